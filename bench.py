@@ -6,15 +6,27 @@ of the ranks' rows to rank 0.  The frame is split into interleaved 8-row stripes
 the N ranks (stripe s -> rank s % N), so the total work is fixed as N grows ("strong").
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5] [--spp S]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: scene and tree build, W warmup frames
+of the benchmarked kernel, the K timed frames (each compared, pixels and rays, with the first
+warmup frame), the JSON line.  --dump-outputs DIR then writes the last timed frame as rank 0
+holds it (DIR/frame.npy, float32, height x width x channels, row 0 = bottom) and that frame's
+counters (DIR/stats.npy, float64: rays, paths); scene, seed and sample streams are fixed, so two
+builds run with the same arguments can be compared array for array.  --full adds everything else
+described below: the reference-order frame (it replaces the first warmup frame, and every frame
+is then compared with it), the `pipelined` figure, `compat_mode`, `interactive`, the dynamic
+scene's device rebuild in `scene_build`, and `cpu_baseline`; the --no-* flags switch single
+parts of --full off.
 
 RNG mode (--rng): `sample` (default) draws each pixel-sample from its own XORWOW stream seeded
 by Philox, so a frame is a set of independent (pixel, 16-sample block) tasks that persistent
 waves take from a counter: every GPU gets an equal share.  `compat` reproduces the reference's
 per-pixel curand_init(seed, pixel, 0) streams bit for bit; a pixel's 1024 samples are then one
 sequential chain, and the slowest pixels (paths trapped under the bunny, ~40 rays each) bound
-the frame at ~1.8 s however many GPUs share it.  At N = 1 the line also carries one compat frame
-(`compat_mode`).  Both modes render the same image in distribution (tests/test_oracle.py).
+the frame at ~1.8 s however many GPUs share it.  With --full at N = 1 the line also carries one
+compat frame (`compat_mode`).  Both modes render the same image in distribution (tests/test_oracle.py).
 
 Kernel (--kernel): `wide` (default) traverses the compressed 8-wide SAH tree nearest child
 first and keeps the reference's closest hit by (t, the reference's tie order); `wavefront` walks
@@ -27,12 +39,13 @@ binary, 80 B 8-wide compressed -- + 40 B per triangle test + 20 B per sphere tes
 time from HIP events on the render stream, against the L2 ceiling (the tree is L2-resident; the
 HBM fraction of the PMC traffic is reported beside it).  PMC-derived fields (traffic, VALU
 instructions) come from the committed profiles of the SAME libpt.so build (`build_id`, sha256),
-else null.  `cpu_baseline` = the CPU restatement (oracle/) on the host cores, rank 0 at N = 1 only,
-on a bounded sample.  `interactive` (N = 1) = frames/s of the progressive interactive mode at
-1 / 4 / 16 spp.  Every timed frame is compared with the reference-order kernel's frame (pixels
-and rays).  The headline renders one frame at a time at every N, with the host-built wide tree
-at every N (the same method for N = 1 and N = 8: the driver divides their ms_per_step).  The
-`pipelined` figure beside it repeats the timed sequence with two frames in flight: consecutive
+else null.  `cpu_baseline` (--full) = the CPU restatement (oracle/) on the host cores, rank 0 at
+N = 1 only, on a bounded sample.  `interactive` (--full, N = 1) = frames/s of the progressive
+interactive mode at 1 / 4 / 16 spp.  With --full every timed frame is compared with the
+reference-order kernel's frame (pixels and rays).  The headline renders one frame at a time at
+every N, with the host-built wide tree at every N (the same method for N = 1 and N = 8: the
+driver divides their ms_per_step).  The `pipelined` figure beside it (--full) repeats the timed
+sequence with two frames in flight: consecutive
 steps alternate between two films on two streams, so a frame's first waves overlap the previous
 frame's tail (7 % of a 1/8 share).  (--frames-in-flight 2 makes that the headline; its roofline
 launch duration is then taken from a warmup launch that ran alone.)
@@ -239,6 +252,14 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (0 = the config's)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the last timed frame (DIR/frame.npy, float32, height x width x channels) "
+                         "and its counters (DIR/stats.npy, float64: rays, paths) after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also: the reference-order frame and every frame's comparison with it, the `pipelined` "
+                         "figure, compat_mode, interactive, the dynamic scene's rebuild and cpu_baseline (a plain "
+                         "run sets up, warms up, times the steps and prints the line); the --no-* flags below "
+                         "switch single parts of it off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--leaf-batch", type=int, default=0, help="wavefront LEAF threshold (0 = library default)")
     ap.add_argument("--shade-batch", type=int, default=0, help="wavefront SHADE threshold (0 = library default)")
@@ -409,20 +430,29 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
                         gather_host_ms[0] += (time.perf_counter() - tg0) * 1e3
         return st
 
-    # Warmup 1 uses the ray-synchronous kernel, whose traversal follows the reference's node
+    # With --full, warmup 1 uses the ray-synchronous kernel, whose traversal follows the reference's node
     # order exactly: its counters give the frame's ALGORITHMIC bytes (the wavefront kernel may
     # visit a few extra nodes speculatively; those are not counted as useful work).  Both
     # kernels produce the identical frame (same rays, same primitive tests, same pixels).
     # (An instanced scene has only the wide kernel: its first frame is the one later frames equal.)
-    phase("reference-order frame")
-    ref_st = frame(0, ptamd.KERNEL_WIDE if instanced else ptamd.KERNEL_SIMPLE, wait=True)
-    ref_buf.copy_(local_bufs[0])
-    failed = []   # this rank's frames that differ from the reference-order frame
+    # A plain run (no --full) renders no reference-order frame: the first frame of the benchmarked
+    # kernel (warmup 1) is then the one every later frame is compared with.
+    ref_st = None
+    ref_name = "reference-order" if args.full else "first warmup"
+    if args.full:
+        phase("reference-order frame")
+        ref_st = frame(0, ptamd.KERNEL_WIDE if instanced else ptamd.KERNEL_SIMPLE, wait=True)
+        ref_buf.copy_(local_bufs[0])
+    failed = []   # this rank's frames that differ from the reference frame
 
     def check(st, j, where):
-        # every frame: this rank's pixels and ray count equal the reference-order frame's.  A
+        # every frame: this rank's pixels and ray count equal the reference frame's.  A
         # mismatch is recorded, not raised: all ranks learn of it together (agree) and exit with it.
+        nonlocal ref_st
         with torch.cuda.stream(streams[j]):
+            if ref_st is None:   # a plain run's first frame: the reference of the later ones
+                ref_buf.copy_(local_bufs[j])
+                ref_st = st
             same = torch.equal(local_bufs[j], ref_buf)
         if injected(rank, where) == "mismatch":
             same = False
@@ -435,7 +465,7 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
         # every rank's checks so far; any failure ends EVERY rank with status 3 (N = 1: this rank)
         bad = ptdist.agree(not failed, dev if backend == "nccl" else "cpu") if dist_on else ([rank] if failed else [])
         if bad:
-            raise SystemExit(f"frame differs from the reference-order frame on rank(s) {bad} ({where}; "
+            raise SystemExit(f"frame differs from the {ref_name} frame on rank(s) {bad} ({where}; "
                              f"this rank: {failed or 'ok'})")
 
     def finish(j, where="timed frames"):
@@ -443,18 +473,20 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
         check(st, j, where)
         return st
 
-    check(ref_st, 0, "reference-order frame")   # (also loads torch's comparison kernels before the timed region)
+    if args.full:
+        check(ref_st, 0, "reference-order frame")   # (also loads torch's comparison kernels before the timed region)
     fif = settings["frames_in_flight"]
-    warm_kms = ref_st.kernel_ms
+    warm_kms = ref_st.kernel_ms if args.full else 0.0
     phase("warmup frames")
     if fif == 2:
         st1 = frame(1, wait=True)   # (film 1's first launch: its tile costs for the launch order)
         check(st1, 1, "warmup frames")
         warm_kms = st1.kernel_ms
-    # (the reference-order frame above counts as one warmup step; the benchmarked kernel gets at least
-    # one warmup frame of its own, so its first use -- the wide tree's host build, module loading --
-    # never falls into the timed region)
-    for k in range(max(1, args.warmup - 1) if args.warmup > 0 else 0):
+    # (--full: the reference-order frame above counts as one warmup step; the benchmarked kernel gets at
+    # least one warmup frame of its own, so its first use -- the wide tree's host build, module loading --
+    # never falls into the timed region.  A plain run: --warmup frames of the benchmarked kernel)
+    n_warm = args.warmup if not args.full else (max(1, args.warmup - 1) if args.warmup > 0 else 0)
+    for k in range(n_warm):
         stw = frame(k % fif, wait=True)
         check(stw, k % fif, "warmup frames")
         warm_kms = stw.kernel_ms
@@ -479,8 +511,9 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
         last_st = st
         rays += st.rays
         # algorithmic bytes of the tree the kernel traverses: the wide kernel's own visits; the
-        # binary kernel's reference-order visits (its speculative extra visits are not work)
-        kbytes += st.algo_bytes if args.kernel == "wide" else ref_st.algo_bytes
+        # binary kernel's reference-order visits (its speculative extra visits are not work; a plain
+        # run has no reference-order frame and takes the kernel's own counts)
+        kbytes += st.algo_bytes if args.kernel == "wide" or not args.full else ref_st.algo_bytes
         spec_visits += st.node_visits
         kms += st.kernel_ms
 
@@ -499,6 +532,14 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
     st = last_st   # (the last timed frame's counters)
     phase("reduce")
     agree("timed frames")
+
+    def last_frame():
+        # the last timed frame as rank 0 holds it (N > 1: the ranks' stripes un-permuted)
+        if dist_on:
+            img = ptdist.assemble(gathered[last], h, w, STRIPE, world, chans)
+            torch.cuda.synchronize(dev)
+            return img
+        return local_bufs[last][: h * w * chans]
 
     tdev = dev if backend == "nccl" else "cpu"
     gather_ms = sum(a.elapsed_time(b) for a, b in gather_ev) if gather_ev else gather_host_ms[0]
@@ -521,6 +562,15 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
                      "wall_ms_per_frame": float(v[3])} for r, v in enumerate(torch.stack(allr).cpu().tolist())]
     else:
         total_rays = float(rays)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # what a caller of the timed path receives: the frame (RGBA8 values or linear-sqrt RGB, as
+        # float32) and its closest-hit queries (all ranks).  Written before any later part of the
+        # run renders into the buffers again.
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "frame.npy"),
+                last_frame().reshape(h, w, chans).cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "stats.npy"),
+                np.array([total_rays / args.steps, float(w * h * spp)], dtype=np.float64))
     if fif > 1 and args.steps > 0:
         # one frame alone (no frame in flight beside it): its latency, max over ranks, beside the
         # pipelined ms_per_step
@@ -540,7 +590,7 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
         single_frame_ms = float(sf.item())
         agree("single frame")
     pipelined = None
-    if args.steps > 0 and fif == 1 and not args.no_pipelined:
+    if args.full and args.steps > 0 and fif == 1 and not args.no_pipelined:
         # The same timed sequence with two frames in flight (films 0 / 1 on two streams, each frame
         # still rendered in full, gathered and checked): the launches' tails overlap the next frame's
         # first waves.  Reported beside the one-frame-at-a-time headline, never instead of it.
@@ -578,7 +628,7 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
     phase("report")
 
     compat = None
-    if sample and world == 1 and not args.no_compat:
+    if args.full and sample and world == 1 and not args.no_compat:
         # the reference's RNG semantics on the same frame, for comparison (2 frames: the first
         # measures tile costs for the longest-first launch order, the second is timed)
         for it in range(2):
@@ -596,13 +646,8 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
                           "oracle/), one frame after one warmup"}
 
     if rank == 0:
-        if dist_on:   # un-permute the stripes of the last frame (rank 0 holds the full image)
-            img = ptdist.assemble(gathered[last], h, w, STRIPE, world, chans)
-            torch.cuda.synchronize(dev)
-        else:
-            img = local_bufs[last][: h * w * chans]
         if args.png:
-            a = img.reshape(-1).cpu().numpy()
+            a = last_frame().reshape(-1).cpu().numpy()
             if rgba8:
                 ptamd.write_png_rgba8(args.png, a, w, h)
             else:
@@ -627,6 +672,7 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "strong",
@@ -665,8 +711,11 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
                                                "triangle test + 20 B per sphere test" if args.kernel == "wide" else
                                                "reference-order traversal counts of the same frame (ray-synchronous "
                                                "kernel, warmup step 1): 56 B per binary node visit + 40 B per "
-                                               "triangle test + 20 B per sphere test"),
-                         "node_visits_reference": ref_st.node_visits,
+                                               "triangle test + 20 B per sphere test" if args.full else
+                                               "the wavefront kernel's own counts, speculative visits included "
+                                               "(--full: the reference-order traversal's): 56 B per binary node "
+                                               "visit + 40 B per triangle test + 20 B per sphere test"),
+                         "node_visits_reference": ref_st.node_visits if args.full else None,
                          "node_visits_kernel": spec_visits / args.steps,
                          # the kernel's binding resource: VALU instruction
                          # issue, its wave-instructions per launch (PMC) / kernel time vs the ceiling
@@ -688,16 +737,16 @@ def run(args, world: int, rank: int, local: int, backend: str, dev, dist_on: boo
             out["pipelined"] = pipelined
         if compat:
             out["compat_mode"] = compat
-        if world == 1 and not args.no_interactive:
+        if args.full and world == 1 and not args.no_interactive:
             out["interactive"] = interactive(scene, preset, dev, stream, local)
-        if world == 1 and not instanced:   # a dynamic scene's per-frame rebuild: LBVH + wide tree on the device
+        if args.full and world == 1 and not instanced:   # a dynamic scene's per-frame rebuild: LBVH + wide tree on the device
             dyn = ptamd.Scene(preset.objects, preset.materials, device=local,
                               flags=ptamd.PT_BVH_ORIGIN_BOUNDS | ptamd.PT_BVH_WIDE_DEVICE)
             dyn.build_bvh(ptamd.PT_BVH_ORIGIN_BOUNDS | ptamd.PT_BVH_WIDE_DEVICE)   # a rebuild: buffers reused
             scene_build["lbvh_plus_wide_tree_device_ms"] = dyn.build_ms
             del dyn
         out["scene_build"] = scene_build
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             gpu_ref = None if instanced else {
                 "gpu_reference_order_node_visits": ref_st.node_visits / max(ref_st.rays, 1),
                 "gpu_reference_order_prim_tests": (ref_st.tri_tests + ref_st.sphere_tests) / max(ref_st.rays, 1),

@@ -163,3 +163,13 @@ def test_bench_method_is_the_same_at_every_n(monkeypatch):
     assert {bench.run_settings(args, n)["wide_tree"] for n in (1, 8)} == {"device"}
     two = bench.make_parser().parse_args(["--frames-in-flight", "2"])
     assert {bench.run_settings(two, n)["frames_in_flight"] for n in (1, 8)} == {2}
+
+
+def test_bench_plain_run_is_the_default():
+    """--full is off unless asked for (a plain run times its steps and nothing else), and the
+    driver's plain command line parses with --dump-outputs."""
+    import bench
+    args = bench.make_parser().parse_args(["--gpus", "1", "--steps", "5", "--warmup", "3"])
+    assert args.full is False and args.dump_outputs == "" and (args.steps, args.warmup) == (5, 3)
+    args = bench.make_parser().parse_args(["--full", "--dump-outputs", "out"])
+    assert args.full is True and args.dump_outputs == "out"

@@ -66,8 +66,8 @@ def test_bench_two_ranks_reassemble_one_rank_frame(tmp_path):
     import sys
     from helpers import failure_digest, last_json, read_png, run_logged
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["bench.py", "--config", "c2", "--spp", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-              "--no-compat"]
+    common = ["bench.py", "--config", "c2", "--spp", "4", "--steps", "2", "--warmup", "1", "--full",
+              "--no-cpu-baseline", "--no-compat"]
     one, two = str(tmp_path / "one.png"), str(tmp_path / "two.png")
     rc, log1, _ = run_logged([sys.executable] + common + ["--png", one], 150, cwd=repo, log_path=tmp_path / "r1.log")
     assert rc == 0, log1[-3000:]
@@ -101,7 +101,7 @@ def test_bench_failing_rank_ends_every_rank(tmp_path, kind):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     where = "timed frames" if kind == "mismatch" else "timed"
     cmd = _torchrun(2) + ["bench.py", "--gpus", "2", "--config", "c2", "--spp", "4", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-compat"]
+                          "--full", "--no-cpu-baseline", "--no-compat"]
     env = _rank_env(PT_DIST_BACKEND="gloo", PT_BENCH_INJECT=f"1:{where}:{kind}", PT_DIST_TIMEOUT="20",
                     PT_BENCH_WATCHDOG="40", TORCHELASTIC_ERROR_FILE=str(tmp_path / "err.json"))
     rc, log, wall = run_logged(cmd, 240, cwd=repo, env=env, log_path=tmp_path / "fail.log")
@@ -127,8 +127,8 @@ def test_bench_rccl_gather_one_rank(tmp_path, fif):
     import sys
     from helpers import last_json, read_png, run_logged
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["bench.py", "--config", "c2", "--spp", "4", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-              "--no-compat", "--no-interactive"]
+    common = ["bench.py", "--config", "c2", "--spp", "4", "--steps", "1", "--warmup", "1", "--full",
+              "--no-cpu-baseline", "--no-compat", "--no-interactive"]
     one, forced = str(tmp_path / "one.png"), str(tmp_path / "rccl.png")
     rc, log1, _ = run_logged([sys.executable] + common + ["--png", one], 150, cwd=repo, log_path=tmp_path / "r1.log")
     assert rc == 0, log1[-3000:]
@@ -156,8 +156,8 @@ def test_bench_c4_eight_ranks_rehearsal(tmp_path):
     import sys
     from helpers import failure_digest, last_json, read_png, run_logged
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["bench.py", "--config", "c4", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-compat",
-              "--no-interactive"]
+    common = ["bench.py", "--config", "c4", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline",
+              "--no-compat", "--no-interactive"]
     one, eight = str(tmp_path / "one.png"), str(tmp_path / "eight.png")
     rc, log1, _ = run_logged([sys.executable] + common + ["--png", one], 240, cwd=repo, log_path=tmp_path / "r1.log")
     assert rc == 0, failure_digest(log1)
@@ -177,6 +177,35 @@ def test_bench_c4_eight_ranks_rehearsal(tmp_path):
     assert len(l8["per_rank"]) == 8 and "wide_tree_host_ms" in l8["scene_build"]
     assert l1["config"]["wide_tree"] == l8["config"]["wide_tree"] == "host"   # one method at N = 1 and N = 8
     assert l1["config"]["frames_in_flight"] == l8["config"]["frames_in_flight"] == 1
+
+
+@pytest.mark.timeout(200)
+def test_bench_plain_run_dumps_its_last_frame(tmp_path):
+    """A plain run (no --full) times exactly --steps frames and carries none of the figures that
+    --full adds; --dump-outputs writes the last timed frame as float32 (the values of the PNG
+    of the same run) and its counters."""
+    import os
+    import sys
+    from helpers import last_json, read_png, run_logged
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    png, dump = str(tmp_path / "plain.png"), str(tmp_path / "dump")
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--config", "c2", "--spp", "4", "--steps", "3", "--warmup", "1",
+           "--png", png, "--dump-outputs", dump]
+    rc, log, _ = run_logged(cmd, 150, cwd=repo, log_path=tmp_path / "plain.log")
+    assert rc == 0, log[-3000:]
+    b = last_json(log)
+    assert b["steps"] == 3 and b["warmup"] == 1 and b["full"] is False
+    assert b["ms_per_step"] > 0 and b["value"] > 0 and b["unit"] == "Mray/s" and b["dtype"] == "f32"
+    for k in ("pipelined", "compat_mode", "interactive", "cpu_baseline"):
+        assert k not in b, k
+    assert sorted(os.listdir(dump)) == ["frame.npy", "stats.npy"]
+    frame, stats = np.load(os.path.join(dump, "frame.npy")), np.load(os.path.join(dump, "stats.npy"))
+    assert frame.dtype == np.float32 and frame.shape == (b["config"]["height"], b["config"]["width"], 4)
+    # (the frame's rows as rendered, row 0 = bottom; the PNG writer flips them)
+    np.testing.assert_array_equal(frame, read_png(png)[::-1].astype(np.float32))
+    assert frame[..., :3].max() > 0
+    assert stats.dtype == np.float64
+    assert stats[0] == b["config"]["rays_per_frame"] and stats[1] == frame.shape[0] * frame.shape[1] * 4
 
 
 @pytest.mark.timeout(200)

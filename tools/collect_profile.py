@@ -5,7 +5,7 @@ build id (sha256 of libpt.so) the run measured: bench.py reports the counters on
 
 HBM bytes per launch = 2 x FETCH_SIZE + WRITE_SIZE (rocprofv3 reports both in KiB; on gfx950
 FETCH_SIZE counts half of the bytes of 128-B requests, MI355X_MICROARCH.md "HBM"), taken from the
-wavefront render launch of `bench.py --steps 1 --warmup 0 --no-compat` (warmup launch 1 is the
+wavefront render launch of `bench.py --full --steps 1 --warmup 0 --no-compat` (warmup launch 1 is the
 ray-synchronous kernel, launch 2 the timed wavefront kernel).
 
     python tools/collect_profile.py r01_final

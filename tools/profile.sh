@@ -1,6 +1,6 @@
 #!/bin/bash
 # Bench + rocprofv3 session on the GPU box (run via gpurun).  TAG names the output dir.
-#  1. python bench.py (the driver's default command)          -> gpurun_out/$TAG/bench.json
+#  1. python bench.py --full (every figure of the line)        -> $OUT/bench.json
 #  2. rocprofv3 --kernel-trace --stats of the same frames (without the CPU baseline and the
 #     interactive-mode frames, whose 1-16 spp launches would mix into the render kernel's average,
 #     and without the `pipelined` frames, whose overlapping launches last longer than a frame)
@@ -15,8 +15,8 @@ TAG=${TAG:-prof}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 BENCH_ARGS=${BENCH_ARGS:-}
-PMC_ARGS=${PMC_ARGS:---steps 1 --warmup 1 --no-cpu-baseline --no-compat --no-interactive --no-pipelined}
-TRACE_ARGS=${TRACE_ARGS:---no-cpu-baseline --no-interactive --no-pipelined}
+PMC_ARGS=${PMC_ARGS:---steps 1 --warmup 1 --full --no-cpu-baseline --no-compat --no-interactive --no-pipelined}
+TRACE_ARGS=${TRACE_ARGS:---full --no-cpu-baseline --no-interactive --no-pipelined}
 step() {  # name, limit, command...
     local name=$1 lim=$2; shift 2
     timeout -k 10 $lim "$@" > $OUT/$name.log 2>&1
@@ -24,7 +24,7 @@ step() {  # name, limit, command...
     echo "$name rc=$rc"; tail -2 $OUT/$name.log | cut -c1-400
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
-step bench 600 python bench.py $BENCH_ARGS
+step bench 600 python bench.py --full $BENCH_ARGS
 grep '^{' $OUT/bench.log > $OUT/bench.json
 step trace 900 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py $TRACE_ARGS $BENCH_ARGS
 step pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o run --output-format csv -- python3 bench.py $PMC_ARGS $BENCH_ARGS
