@@ -56,29 +56,11 @@ int compatWideWavesPerCU(int stack, int& n);                            // pt_co
 namespace {
 
 constexpr int kWave = 64;
-#ifndef PT_AB_NO_ATOMICS
-#define PT_AB_NO_ATOMICS 0
-#endif
-// Time-only A/B switches (wrong images; DESIGN.md section 11's VALU budget): the Lambertian
-// rejection loop cut to its first trial; the sample-mode Philox seeding replaced by a two-multiply
-// hash; the ray start without its MIX-range check and with a bare v_rcp_f32.
-#ifndef PT_FIXED_SMALL
-#define PT_FIXED_SMALL 1   // sample mode: blockFixedSmall when every finishing lane's sums are in [0, 2^24)
-#endif
-#ifndef PT_AB_ONE_TRIAL
-#define PT_AB_ONE_TRIAL 0
-#endif
-#ifndef PT_AB_CHEAP_SEED
-#define PT_AB_CHEAP_SEED 0
-#endif
-#ifndef PT_AB_CHEAP_START
-#define PT_AB_CHEAP_START 0
-#endif
 constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr uint32_t kSphereBit = 0x40000000u;
 constexpr uint32_t kPrimMask = 0x3fffffffu;
-constexpr int kJumpMats = 32;
-constexpr int kNumCounters = 32;                 // per-scene u64 counters: work counts, error word, diagnostics                    // XORWOW 2^(67+k) jump matrices, k < 32
+constexpr int kJumpMats = 32;                    // XORWOW 2^(67+k) jump matrices, k < 32
+constexpr int kNumCounters = 32;                 // per-scene u64 counters: work counts, error word, diagnostics
 
 // ------------------------------------------------------------------------ device structs
 struct DevScene {
@@ -139,19 +121,13 @@ __device__ __forceinline__ float3 normalize3(float3 v) {
 __device__ __forceinline__ float3 xyz(float4 v) { return f3(v.x, v.y, v.z); }
 
 // ------------------------------------------------------------------------ XORWOW
-#ifndef PT_XORWOW_BITOP3
-#define PT_XORWOW_BITOP3 1
-#endif
 struct Xorwow {
     uint32_t d, v0, v1, v2, v3, v4;
     __device__ __forceinline__ uint32_t next() {   // curand(curandStateXORWOW*)
         uint32_t t = v0 ^ (v0 >> 2);
         v0 = v1; v1 = v2; v2 = v3; v3 = v4;
-#if PT_XORWOW_BITOP3   // the three-way XOR in one v_bitop3_b32 (gfx950): six VALU per draw instead of seven
+        // the three-way XOR in one v_bitop3_b32 (gfx950): six VALU per draw instead of seven
         v4 = __builtin_amdgcn_bitop3_b32(v4, v4 << 4, t ^ (t << 1), 0x96);
-#else
-        v4 = (v4 ^ (v4 << 4)) ^ (t ^ (t << 1));
-#endif
         d += 362437u;
         return v4 + d;
     }
@@ -166,12 +142,6 @@ struct Xorwow {
 // then cost a few shifts each (the reference's generator family, curand_uniform mapping).
 // Any sample of any pixel starts anywhere, in one block of work.
 __device__ __forceinline__ Xorwow sampleStream(uint32_t k0, uint32_t k1, uint32_t sample, uint32_t pixel) {
-#if PT_AB_CHEAP_SEED   // (A/B timing only: no Philox rounds)
-    {
-        const uint32_t a = (sample ^ k0) * 0x9E3779B9u, b = (pixel ^ k1) * 0x85EBCA6Bu;
-        return Xorwow{a, a ^ b, b + 0x6C078965u, a + b, (a ^ 0x2545F491u) | 1u, b ^ 0x53414D50u};
-    }
-#endif
     uint32_t c0 = sample, c1 = pixel, c2 = 0u, c3 = 0x53414D50u;
 #pragma unroll 2   // (pairs of rounds: no register moves; a full unroll raises the camera-ray site's pressure)
     for (int r = 0; r < 10; r++) {
@@ -179,11 +149,8 @@ __device__ __forceinline__ Xorwow sampleStream(uint32_t k0, uint32_t k1, uint32_
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
         const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
         const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-#if PT_XORWOW_BITOP3   // (three-way XORs as one v_bitop3_b32 each)
+        // (three-way XORs as one v_bitop3_b32 each)
         const uint32_t n0 = __builtin_amdgcn_bitop3_b32(hi1, c1, k0, 0x96), n2 = __builtin_amdgcn_bitop3_b32(hi0, c3, k1, 0x96);
-#else
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-#endif
         c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
@@ -447,43 +414,6 @@ __device__ __forceinline__ void wideTest(const Prim& q, float3 o, float3 d, floa
     }
 }
 
-// wideTest's decisions on a primitive another lane tested (the wave-cooperative LEAF step): t from
-// primHitAny, key = its rank | kSphereBit for a sphere, blo = its exact leaf box's entry distance
-// (aabb::hit with tmax = inf) or -1 when that box is missed (an entry is >= tmin > 0).  Applied in
-// the group's order, the same updates of closest / best / bestLo / redo as wideTest.
-template <bool SPH>
-__device__ __forceinline__ void wideMerge(float t, uint32_t key, float blo, float& closest, int& best, float& bestLo,
-                                          bool leafBoxes, bool& redo) {
-    if (t >= 0.0f) {
-        const bool sph = SPH && (key & kSphereBit) != 0u;
-        const int k = (int)(key & kPrimMask);
-        const bool none = best < 0, bSph = SPH && (best & (int)kSphereBit) != 0;
-        const int bk = SPH ? best & (int)kPrimMask : best;
-        const bool tie = sph ? (none || !bSph || k > bk) : (!none && !bSph && k < bk);
-        redo = redo || (t >= closest && t < bestLo);
-        if (t < closest || (t == closest && tie)) {
-            bool take = true;
-            float lo = -__builtin_inff();
-            if (leafBoxes) {
-                const bool bh = blo >= 0.0f;
-                take = bh && !(closest < blo);
-                redo = redo || (bh && closest < blo);
-                lo = t < blo ? blo : lo;
-            }
-            if (take) {
-                closest = t;
-                best = k | (sph ? (int)kSphereBit : 0);
-                bestLo = lo;
-            }
-        }
-    }
-}
-
-// Lanes below this one whose bit is set in m (v_mbcnt_lo / v_mbcnt_hi).
-__device__ __forceinline__ __attribute__((unused)) uint32_t mbcnt64(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
 // One compressed 8-wide node (five 16-B words, layout in host/pt_wide8.cpp) against the ray:
 // returns the hit mask, internal children in bits 24 + (slot ^ oct), leaf primitives in bits
 // 0..23 (offsets from the node's primitive base).  Plane distances t = q * (s * inv) + (p - o) *
@@ -617,10 +547,7 @@ __device__ __forceinline__ uint32_t wideHitsInst(uint4 n0, uint4 n1, uint4 n2, u
 
 // The ray origin lies farther than 8 scene extents from the scene's centre on some axis, beyond
 // the distance the wide boxes' margin covers (wideHits): the query runs in the reference's order.
-#ifndef PT_WIDE_FAR_EXT
-#define PT_WIDE_FAR_EXT 8.0f   // with the builders' PT_WIDE_EMIN_SHIFT 18 (host/pt_wide8.cpp)
-#endif
-constexpr float kWideFarExt = PT_WIDE_FAR_EXT;
+constexpr float kWideFarExt = pt::kW8FarExt;   // tied to the builders' quantum in host/pt_wide8.hpp
 __device__ __forceinline__ bool wideFar(float cx, float cy, float cz, float ext, float3 o) {
     const float m = fmaxf(fmaxf(fabsf(o.x - cx), fabsf(o.y - cy)), fabsf(o.z - cz));
     return !(m <= kWideFarExt * ext);   // (NaN: far)
@@ -850,7 +777,7 @@ __device__ __forceinline__ float3 onUnitSphere(G& g) {
         const float cz = g.centered2();
         res = f3(a, b, cz);
         norm = len2(res);
-    } while (!PT_AB_ONE_TRIAL && norm >= 1.0f);
+    } while (norm >= 1.0f);
     return divs(res, sqrtf(norm));
 }
 template <class G>
@@ -1001,10 +928,8 @@ struct RenderParams {
     // (blockFixed), with atomics: integer addition is exact and order-free, so the image does
     // not depend on scheduling or on the stripe partition.  pixAcc[4 * pixel] = {x, y, z, rays}.
     int nblocks, block;
-    // A task covers `group` consecutive summation blocks of one pixel (`span` = group x block samples;
-    // ngroups spans per pixel): each block's fixed-point sum is added into the lane's LDS partial,
-    // and the task adds the partial to the pixel's accumulator once (3 global atomics per task, not
-    // per block).  The fixed-point additions are exact and order-free: the image does not change.
+    // A task is one summation block: `span` = block samples, `ngroups` = nblocks tasks per pixel
+    // (`group` = 1; the field only keeps the layout).
     int group, span, ngroups;
     unsigned long long* pixAcc;
     unsigned* taskCounter;                    // next task (zeroed before the launch)
@@ -1016,7 +941,7 @@ struct RenderParams {
     int measureCost;                          // sample mode: count rays per pixel for the tile order
     int camFar;                               // wide: the camera lies beyond the wide boxes' margin (wideFar)
     int rawOut;                               // compat: store the raw sample sum (resolveKernel follows)
-    int stripeShift, blockShift;              // log2(stripe_h), log2(block) when powers of two, else -1
+    int stripeShift, blockShift;              // log2(stripe_h), log2(block) when powers of two, else -1 (blockShift: no reader left)
     int splitTiles, splitWays;                // compat: the longest tiles run as splitWays waves each
     int compatGrid;                           // compat (tile waves): critWaves + ntiles + splitTiles * (splitWays - 1)
     // compat, critical pixels (wide kernel): the nCrit pixels of critList (the previous launch's
@@ -1029,11 +954,6 @@ struct RenderParams {
     uint32_t* pixRays;
 };
 
-// (blockFixed, blockFixedSmall, fixedToFloat: pt_math.hpp)
-// One finished (pixel, block) task: its sum added to the pixel's accumulator, and -- on frames
-// that measure tile costs (`cost`: the input of the next launches' longest-first order) -- its ray
-// count; no-return atomics (device scope: 4 of them per task cost 5 % of a C3 frame, so the ray
-// counts are taken on one frame in eight).
 // compat critical pixels: how many (PT_CRIT_PIXELS) and how many per wave (PT_CRIT_LANES)
 #ifndef PT_CRIT_PIXELS
 #define PT_CRIT_PIXELS 256
@@ -1045,25 +965,21 @@ constexpr int kCritPixels = PT_CRIT_PIXELS;
 constexpr int kCritLanes = PT_CRIT_LANES;
 // which compat kernels have critical-pixel waves: the flattened wide tree on shallow trees (stack 8:
 // the 4-waves/SIMD compat kernels, whose 128-VGPR budget holds the per-lane loop without spills)
-__host__ __device__ constexpr bool critFor(bool sample, bool wide, bool inst, bool cq, int stack) {
-    return !sample && wide && !inst && !cq && stack <= 8;
+__host__ __device__ constexpr bool critFor(bool sample, bool wide, bool inst, int stack) {
+    return !sample && wide && !inst && stack <= 8;
 }
-__device__ __forceinline__ __attribute__((unused)) void addFixed1(unsigned long long* acc, unsigned long long v) {
-#if PT_AB_NO_ATOMICS
-    return;
-#endif
-    __hip_atomic_fetch_add(acc, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// (blockFixed, blockFixedSmall, fixedToFloat: pt_math.hpp)
+// One finished (pixel, block) task: its sum added to the pixel's accumulator, and -- on frames
+// that measure tile costs (`cost`: the input of the next launches' longest-first order) -- its ray
+// count; no-return atomics (device scope: 4 of them per task cost 5 % of a C3 frame, so the ray
+// counts are taken on one frame in eight).
 __device__ __forceinline__ void addBlock(unsigned long long* acc, float3 sum, uint32_t rays, bool cost) {
-#if PT_AB_NO_ATOMICS
-    return;
-#endif
     // the common case -- every finishing lane's three sums in [0, 2^24), NaN excluded by the >= 0
     // tests -- takes blockFixedSmall (a wave-uniform branch on the ballot)
     const bool small = sum.x >= 0.0f && sum.y >= 0.0f && sum.z >= 0.0f &&
                        fmaxf(fmaxf(sum.x, sum.y), sum.z) < 16777216.0f;
     unsigned long long fx, fy, fz;
-    if (PT_FIXED_SMALL && __ballot(!small) == 0) {
+    if (__ballot(!small) == 0) {
         fx = blockFixedSmall(sum.x); fy = blockFixedSmall(sum.y); fz = blockFixedSmall(sum.z);
     } else {
         fx = blockFixed(sum.x); fy = blockFixed(sum.y); fz = blockFixed(sum.z);
@@ -1261,21 +1177,6 @@ constexpr int kLeafQ = PT_LEAF_QUEUE;
 #define PT_TASK_POOL 64
 #endif
 constexpr int kTaskPool = PT_TASK_POOL;   // sample mode: tasks a wave reserves per atomic
-// Experiment (off): XCD-local task pools.  The tile slots are dealt to 8 counters (slot % 8), a
-// wave drains the counter of its XCD (blockIdx % 8: workgroups are dispatched to the XCDs round
-// robin) and then the others in turn, so each XCD's L2 sees the rays of an eighth of the tiles
-// in flight.  Exact by construction: the image does not depend on which lane runs a task.
-#ifndef PT_XCD_POOLS
-#define PT_XCD_POOLS 0
-#endif
-static_assert(!PT_XCD_POOLS || PT_TASK_POOL == 64, "XCD pools hand out whole (tile, block) groups");
-#ifndef PT_TASK_GROUPS
-#define PT_TASK_GROUPS 0   // wide sample kernels: tasks of several summation blocks (LDS partials; measured slower)
-#endif
-#ifndef PT_TASK_BLOCKS
-#define PT_TASK_BLOCKS 2
-#endif
-constexpr int kTaskBlocks = PT_TASK_BLOCKS;   // sample mode: summation blocks per task (PT_TASK_BLOCKS env overrides)
 // Occupancy target of the wavefront kernel (waves per SIMD; 6 = at most 80 VGPRs).  The LDS
 // stack (STACK x 256 B per wave, 160 KB per CU) allows 6 / 5 / 4 / 3 / 2 waves per SIMD at
 // STACK 24 / 32 / 48 / 64 / 80, so deeper trees keep a larger register budget.  Compat tile
@@ -1284,40 +1185,16 @@ constexpr int kTaskBlocks = PT_TASK_BLOCKS;   // sample mode: summation blocks p
 #ifndef PT_WAVES_PER_EU
 #define PT_WAVES_PER_EU 6
 #endif
-#ifndef PT_STACK24
-#define PT_STACK24 1   // STACK 24 instantiations (C3: depth + 1 <= 24): 6 waves per SIMD fit the LDS
-#endif
 #ifndef PT_LDS_STACK
 #define PT_LDS_STACK 32   // sample mode: traversal stack entries per lane kept in LDS
 #endif
 template <int STACK, bool SAMPLE, bool WIDE>
 constexpr int kLdsStack = (!WIDE && STACK > PT_LDS_STACK) ? PT_LDS_STACK : STACK;
-#ifndef PT_AB_NO_SPLIT
-#define PT_AB_NO_SPLIT 0   // (A/B only: compile the compat split-tile prologue out)
-#endif
-#ifndef PT_AB_COST_STORE
-#define PT_AB_COST_STORE 0   // (A/B only: compat tile costs stored, not atomicMax'ed -- wrong with split tiles)
-#endif
-#ifndef PT_COMPAT_QUEUE
-#define PT_COMPAT_QUEUE 0   // compat mode: persistent waves take pixels from a queue (else one wave per tile; 1 measured slower)
-#endif
 #ifndef PT_WIDE_SPEC
 #define PT_WIDE_SPEC 1   // wide kernels: speculative traversal, primitive groups a lane may park while it keeps visiting nodes (0-3)
 #endif
-#ifndef PT_INST_SPEC
-#define PT_INST_SPEC 0   // instanced wide kernels: speculative traversal within an instance's tree (0-1; 1 measured 3 % slower on C5 instanced)
-#endif
 #ifndef PT_WIDE_MIX
 #define PT_WIDE_MIX 1   // wide kernels: plane distances by v_perm + v_fma_mix_f32 (wideHits<MIX>), bit-identical
-#endif
-#ifndef PT_MIX_CHECK
-#define PT_MIX_CHECK 1   // (A/B timing only: 0 drops the per-ray mixUnsafe test -- not exact for near-axis rays)
-#endif
-#ifndef PT_LEAF_COOP
-#define PT_LEAF_COOP 0   // wide kernels (not instanced): wave-cooperative LEAF steps, one (lane, primitive) pair per lane
-#endif
-#ifndef PT_LEAF_COOP_CAP
-#define PT_LEAF_COOP_CAP 2   // pairs a lane offers per cooperative LEAF step (1-3)
 #endif
 #ifndef PT_WIDE_WAVES_PER_EU
 #define PT_WIDE_WAVES_PER_EU 5   // wide tree (96 VGPRs; the stack never limits occupancy): C3 @64 spp 49.7 ms vs 68.8 at 6 (spills), 51.4 at 4
@@ -1384,37 +1261,19 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     __shared__ uint32_t stk[LS * kWave];
     // Wide kernels, speculative traversal: a lane whose primitive group waits for a LEAF step
     // keeps visiting nodes; the waiting group is parked here ({base, bits} per lane; oct bit 4
-    // marks it) and comes back when the current group is empty.
-    constexpr int SPECN = WIDE ? (INST ? PT_INST_SPEC : PT_WIDE_SPEC) : 0;   // parked groups per lane: a stack, count in oct bits 4-5
+    // marks it) and comes back when the current group is empty.  Not in instanced kernels.
+    constexpr int SPECN = WIDE && !INST ? PT_WIDE_SPEC : 0;   // parked groups per lane: a stack, count in oct bits 4-5
     constexpr bool SPEC = SPECN > 0;
     __shared__ uint32_t pend[SPEC ? 2 * SPECN * kWave : 1];
-    // wave-cooperative LEAF steps: the step's queue of (owner lane, primitive) pairs
-    constexpr bool COOP = WIDE && !INST && PT_LEAF_COOP != 0;
-    __shared__ uint32_t leafQ[COOP ? kWave : 1];
-    if constexpr (COOP) leafQ[threadIdx.x] = 0u;   // (every entry is a valid pair from here on)
     // instanced scenes: the lane's world ray {o, d} while it is inside an instance
     __shared__ float wray[INST ? 6 * kWave : 1];
     // sample mode: the lane's task {pixel col | local row << 16, next sample, end sample, rays}.
     // Only SHADE steps (per sample, not per node or primitive) touch it, so it lives in LDS, not
     // in four VGPRs carried through every step.
     __shared__ uint4 taskState[SAMPLE ? kWave : 1];
-    // compat mode with the pixel queue (CQ): the lane's pixel {its tile, rays traced for it, its
-    // index} (LDS: only a pixel's first and last sample touch it)
-    constexpr bool CQ = !SAMPLE && PT_COMPAT_QUEUE != 0;
-    __shared__ uint4 pixState[CQ ? kWave : 1];
-    // sample mode, tasks of several blocks: the task's closed blocks so far, per lane (x, y, z)
-    // (wide kernels; the binary ones take one block per task and keep their LDS for the stack)
-    constexpr bool GROUPS = PT_TASK_GROUPS && SAMPLE && WIDE && STACK <= 16;   // (STACK 24: the LDS would cap occupancy)
-    __shared__ unsigned long long accPart[GROUPS ? 3 * kWave : 1];
-    if constexpr (GROUPS) {
-        accPart[threadIdx.x] = 0ull; accPart[kWave + threadIdx.x] = 0ull; accPart[2 * kWave + threadIdx.x] = 0ull;
-    }
     const int lane = threadIdx.x;
-    // compat mode: all spp of a pixel in order (its per-pixel XORWOW stream).  Default: one wave =
-    // one tile (the longest tiles split, below).  The pixel queue (CQ: PT_COMPAT_QUEUE=1, an
-    // experiment, off: measured slower) makes the waves persistent and lets them
-    // take pixels from a global counter (PT_TAKE_PIXELS): a lane whose pixel has all its samples
-    // takes the next pixel.
+    // compat mode: all spp of a pixel in order (its per-pixel XORWOW stream); one wave = one tile
+    // (the longest tiles split, below).
     // sample mode: persistent waves; each lane repeatedly takes a task = (pixel, summation
     // block) from a global counter and sums that block's samples in order (see PT_TAKE_TASKS).
     // `sample` runs to nSamples (compat: spp; sample mode: the end of the task's block, and
@@ -1425,22 +1284,22 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     // steps with fewer other pixels and its chain advances in more of them.
     int bidT = (int)blockIdx.x, slice = -1;
     // compat, critical-pixel waves (CRIT): the first critWaves blocks (wave-uniform)
-    constexpr bool CRITK = critFor(SAMPLE, WIDE, INST, CQ, STACK);
+    constexpr bool CRITK = critFor(SAMPLE, WIDE, INST, STACK);
     const bool crit = CRITK && bidT < P.critWaves;
     if constexpr (CRITK) {
         if (!crit) bidT -= P.critWaves;
     }
-    if constexpr (!SAMPLE && !CQ && !PT_AB_NO_SPLIT) {
+    if constexpr (!SAMPLE) {
         const int ks = P.splitTiles * P.splitWays;   // (uniform)
         if (crit) {
         } else if (bidT < ks) { slice = bidT % P.splitWays; bidT /= P.splitWays; }
         else bidT -= ks - P.splitTiles;
     }
-    int tile = (SAMPLE || CQ || crit) ? -1 : tileOf(P, bidT), nSamples = SAMPLE ? 0 : P.spp;
+    int tile = (SAMPLE || crit) ? -1 : tileOf(P, bidT), nSamples = SAMPLE ? 0 : P.spp;
     int col = 0, lrow = 0;
     bool valid = false;
     uint32_t idx = 0u;
-    if constexpr (!SAMPLE && !CQ) {
+    if constexpr (!SAMPLE) {
         if (crit) {   // a listed pixel per lane (lanes beyond critLanes or the list idle)
             const int k = bidT * P.critLanes + lane;
             valid = lane < P.critLanes && k < P.nCrit;
@@ -1456,7 +1315,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         }
     }
     const unsigned long long tStart = __builtin_amdgcn_s_memrealtime();
-    if (!SAMPLE && !CQ && !crit && bidT < P.prioTiles) {   // wave-uniform condition (s_setprio takes an immediate)
+    if (!SAMPLE && !crit && bidT < P.prioTiles) {   // wave-uniform condition (s_setprio takes an immediate)
         if (P.prioLevel >= 3) __builtin_amdgcn_s_setprio(3);
         else if (P.prioLevel == 2) __builtin_amdgcn_s_setprio(2);
         else __builtin_amdgcn_s_setprio(1);
@@ -1505,8 +1364,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     // sample mode task state: summation block, its tile (cost accounting), rays traced for it
     uint32_t depthPaths = 0;
     uint32_t pxRays = 0;   // compat tile / critical lanes: rays traced for the lane's pixel (P.pixRays)
-    bool needTask = SAMPLE || CQ;
-    uint32_t poolBase = 0u, poolLeft = 0u;   // sample mode / CQ: the wave's reserved tasks (uniform)
+    bool needTask = SAMPLE;
+    uint32_t poolBase = 0u, poolLeft = 0u;   // sample mode: the wave's reserved tasks (uniform)
 
 
     // Start the closest-hit query of (o, d).  (Macros, not lambdas: a [&] closure makes the
@@ -1518,18 +1377,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             if (kargs()->measureCost)                                                             \
                 __hip_atomic_fetch_add(&taskState[lane].w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
         }                                                                                         \
-        if constexpr (CQ) {   /* rays per pixel, likewise */                                     \
-            if (kargs()->measureCost)                                                             \
-                __hip_atomic_fetch_add(&pixState[lane].y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-        }                                                                                         \
         closest = __builtin_inff();                                                               \
         best = -1;                                                                                \
         sp = 0;                                                                                   \
         qn = 0;                                                                                   \
         if constexpr (CRITK) pxRays++;                                                            \
         if constexpr (WIDE) {   /* the root is slot 0 of a virtual node at base 0 */              \
-            if (PT_AB_CHEAP_START) inv = f3(__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y), __builtin_amdgcn_rcpf(d.z)); \
-            else inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));                                    \
+            inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));                                         \
             const uint32_t oc_ = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u); \
             oct = oc_;                                                                            \
             tg = 0u;                                                                              \
@@ -1538,7 +1392,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             /* only camera rays can start far from the scene (a bounce starts on a primitive), and  \
                they all start at the camera: one uniform flag, set on the host (wideFar) */     \
             if (!INST && ((kargs()->camFar && depthLeft + 1 == kargs()->max_depth) ||              \
-                          (PT_WIDE_MIX && PT_MIX_CHECK && !PT_AB_CHEAP_START && mixUnsafe(inv, kargs()->S.mixLim)))) {                  \
+                          (PT_WIDE_MIX && mixUnsafe(inv, kargs()->S.mixLim)))) {                   \
                 ng = 0u;       /* origin far from the scene, or a direction the MIX planes */      \
                 oct |= 8u;     /* cannot take: the query in the reference's order (SHADE's redo) */ \
             }                                                                                     \
@@ -1605,45 +1459,12 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         }                                                                                         \
         if (redo_) oct |= 8u;   /* order-dependent candidate: SHADE repeats the query */           \
     } while (0)
-    // New camera sample: main.cu:284-286 + camera::get_ray (lens sample: lensOffset; time draw skipped).
     // Sample mode: lanes with needTask take the next tasks of the wave's pool, in lane order; an
     // empty pool is refilled with the next kTaskPool tasks of the global counter (one returning
     // atomic, whose latency the wave waits out, per kTaskPool tasks instead of per SHADE step).
     // Task t = (tile slot t / 64 / nblocks in launch order, block (t / 64) % nblocks, pixel
     // t % 64 of the 8x8 tile); tasks off the frame edge are skipped.  Sets `got` for lanes
     // that received a task; lanes that find the counter exhausted stop asking.
-#if PT_XCD_POOLS
-    // counter x holds the groups of tile slots x, x + 8, ...: local group lg = slot / 8 * ngroups +
-    // block.  A wave tries its own XCD's counter first, then the others in turn (no state kept: an
-    // exhausted counter costs a wave one more atomic per refill; the host keeps the overshoot far
-    // from wrapping, ntasks < 2^28); all eight empty: poolBase = ntasks
-#define PT_POOL_REFILL(grab, leader)                                                                \
-    do {                                                                                          \
-        uint32_t gb_ = Q_.ntasks;                                                                 \
-        for (uint32_t i_ = 0; i_ < 8u; i_++) {                                                    \
-            const uint32_t x_ = (blockIdx.x + i_) & 7u;                                           \
-            uint32_t lb_ = 0;                                                                     \
-            if (lane == (leader)) lb_ = atomicAdd(Q_.taskCounter + x_, (grab));                   \
-            lb_ = __builtin_amdgcn_readfirstlane((uint32_t)__shfl((int)lb_, (leader)));           \
-            const uint32_t lg_ = lb_ >> 6, ng_ = (uint32_t)Q_.ngroups;                            \
-            const uint32_t nt_ = (uint32_t)Q_.ntiles;                                             \
-            const uint32_t nLocal_ = x_ < nt_ ? (nt_ - x_ + 7u) >> 3 : 0u;                        \
-            if (lg_ < nLocal_ * ng_) {                                                            \
-                const uint32_t q_ = lg_ / ng_, blk_ = lg_ - q_ * ng_;                              \
-                gb_ = ((8u * q_ + x_) * ng_ + blk_) << 6;                                         \
-                break;                                                                            \
-            }                                                                                     \
-        }                                                                                         \
-        poolBase = gb_;                                                                           \
-    } while (0)
-#else
-#define PT_POOL_REFILL(grab, leader)                                                                \
-    do {                                                                                          \
-        uint32_t b_ = 0;                                                                          \
-        if (lane == (leader)) b_ = atomicAdd(Q_.taskCounter, (grab));                             \
-        poolBase = __builtin_amdgcn_readfirstlane((uint32_t)__shfl((int)b_, (leader)));           \
-    } while (0)
-#endif
 #define PT_TAKE_TASKS(got)                                                                          \
     do {                                                                                          \
         const auto& Q_ = *kargs();                                                                \
@@ -1655,10 +1476,12 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 /* always a full pool: = one (tile, block) group, one task per lane; smaller    \
                    grabs near the end measured slower (1/8 share: 150-158 vs 145 ms) */          \
                 const uint32_t grab_ = (uint32_t)kTaskPool;                                       \
-                PT_POOL_REFILL(grab_, leader_);                                                   \
+                uint32_t b_ = 0;                                                                  \
+                if (lane == leader_) b_ = atomicAdd(Q_.taskCounter, grab_);                       \
+                poolBase = __builtin_amdgcn_readfirstlane((uint32_t)__shfl((int)b_, leader_));    \
                 poolLeft = grab_;                                                                 \
             }                                                                                     \
-            /* wave-uniform: the taken tasks span task groups (tile slot, blocks) g0 and g0 + 1 */ \
+            /* wave-uniform: the taken tasks span task groups (tile slot, block) g0 and g0 + 1 */  \
             const uint32_t base_ = poolBase;                                                      \
             const uint32_t take_ = min((uint32_t)__popcll(m_), poolLeft);                         \
             poolBase += take_;                                                                    \
@@ -1698,71 +1521,6 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             }                                                                                     \
         }                                                                                         \
     } while (0)
-    // Compat mode, pixel queue (CQ): the lanes with needTask take the next pixels of the global queue,
-    // exactly as many as ask (one returning atomic; ranked in lane order by the ballot): queue slot t
-    // = pixel t % 64 of the 8x8 tile in launch slot t / 64 (longest tiles first), so a take spans at
-    // most two tiles.  No pool is reserved ahead: a pixel is a long task (all its samples), and
-    // slots held back by a wave would wait for that wave's lanes while other waves run dry.  A taken
-    // pixel's XORWOW state comes from the film (curand_init(seed, pixel, 0) or where the last frame
-    // left it).  Slots off the frame edge are skipped; lanes that find the queue exhausted stop asking.
-#define PT_TAKE_PIXELS(got)                                                                         \
-    do {                                                                                          \
-        const auto& Q_ = *kargs();                                                                \
-        for (;;) {                                                                                \
-            const uint64_t m_ = __ballot(needTask);                                               \
-            if (m_ == 0) break;                                                                   \
-            const uint32_t n_ = (uint32_t)__popcll(m_);                                           \
-            const int leader_ = __ffsll((unsigned long long)m_) - 1;                              \
-            uint32_t b_ = 0;                                                                      \
-            if (lane == leader_) b_ = atomicAdd(Q_.taskCounter, n_);                               \
-            const uint32_t base_ = __builtin_amdgcn_readfirstlane((uint32_t)__shfl((int)b_, leader_)); \
-            const uint32_t slotA_ = base_ >> 6, slotB_ = slotA_ + 1u;                             \
-            const uint32_t nt_ = (uint32_t)Q_.ntiles;                                             \
-            const uint32_t xyA_ = slotA_ < nt_ ? ((KU32)Q_.tileXY)[__builtin_amdgcn_readfirstlane(slotA_)] : 0u; \
-            const uint32_t xyB_ = slotB_ < nt_ ? ((KU32)Q_.tileXY)[__builtin_amdgcn_readfirstlane(slotB_)] : 0u; \
-            const uint32_t k_ = (uint32_t)__popcll(m_ & ((1ull << lane) - 1ull));                 \
-            if (needTask) {                                                                       \
-                const uint32_t t_ = base_ + k_;                                                   \
-                if ((t_ >> 6) >= nt_) {                                                           \
-                    needTask = false;   /* the queue is exhausted */                               \
-                } else {                                                                          \
-                    const bool hi_ = (t_ >> 6) != slotA_;                                         \
-                    const uint32_t xy_ = hi_ ? xyB_ : xyA_, px_ = t_ & 63u;                       \
-                    const uint32_t tx_ = xy_ & 0xffffu, ty_ = xy_ >> 16;                          \
-                    const int c_ = (int)(tx_ * 8u + (px_ & 7u)), r_ = (int)(ty_ * 8u + (px_ >> 3)); \
-                    if (c_ < Q_.width && r_ < Q_.nrows) {                                           \
-                        needTask = false;                                                         \
-                        got = true;                                                               \
-                        const uint32_t i_ = (uint32_t)r_ * (uint32_t)Q_.width + (uint32_t)c_;     \
-                        pixState[lane] = make_uint4(ty_ * (uint32_t)Q_.tiles_x + tx_, 0u, i_, 0u); \
-                        fcol = (float)c_;                                                         \
-                        frow = (float)globalRowFast(r_, Q_.stripe_h, Q_.stripeShift, Q_.nparts, Q_.part); \
-                        g = Xorwow{Q_.sd[i_], Q_.s0[i_], Q_.s1[i_], Q_.s2[i_], Q_.s3[i_], Q_.s4[i_]}; \
-                        sum = f3(0.0f, 0.0f, 0.0f);                                               \
-                        sample = 0;                                                               \
-                    }                                                                             \
-                }                                                                                 \
-            }                                                                                     \
-        }                                                                                         \
-    } while (0)
-    // CQ: the lane's pixel has all its samples: its result and XORWOW state back to the film, its
-    // ray count into its tile's cost (the longest pixel of the tile: the next launch's order), and
-    // the lane asks for the next pixel.
-#define PT_FINISH_PIXEL()                                                                           \
-    do {                                                                                          \
-        const auto& Q_ = *kargs();                                                                \
-        const uint4 ps_ = pixState[lane];                                                         \
-        const uint32_t i_ = ps_.z;                                                                \
-        float* out_ = Q_.out + 3 * (size_t)i_;   /* (storePixel) */                               \
-        if (Q_.rawOut) {                                                                          \
-            out_[0] = sum.x; out_[1] = sum.y; out_[2] = sum.z;                                    \
-        } else {                                                                                  \
-            out_[0] = sqrtf(sum.x * Q_.invSpp); out_[1] = sqrtf(sum.y * Q_.invSpp); out_[2] = sqrtf(sum.z * Q_.invSpp); \
-        }                                                                                         \
-        Q_.sd[i_] = g.d; Q_.s0[i_] = g.v0; Q_.s1[i_] = g.v1; Q_.s2[i_] = g.v2; Q_.s3[i_] = g.v3; Q_.s4[i_] = g.v4; \
-        if (Q_.measureCost) atomicMax(Q_.tileCost + ps_.x, ps_.y);                                \
-        needTask = true;                                                                          \
-    } while (0)
     // Sample mode: the lane's block (= its task; ts = the task state) is complete: its sum and ray
     // count go to the pixel's accumulator (order-free integer atomics on per-pixel addresses: no
     // contention; right here -- deferring them to a later step of the loop, where fewer registers
@@ -1770,30 +1528,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #define PT_FINISH_TASK(ts)                                                                          \
     do {                                                                                          \
         unsigned long long* acc_ = kargs()->pixAcc + 4 * (size_t)(((ts).x >> 16) * (uint32_t)kargs()->width + ((ts).x & 0xffffu)); \
-        if constexpr (GROUPS) {   /* the task's earlier blocks wait in the lane's LDS partial */ \
-            addFixed1(acc_ + 0, accPart[lane] + blockFixed(sum.x));                               \
-            addFixed1(acc_ + 1, accPart[kWave + lane] + blockFixed(sum.y));                       \
-            addFixed1(acc_ + 2, accPart[2 * kWave + lane] + blockFixed(sum.z));                   \
-            if (kargs()->measureCost) addFixed1(acc_ + 3, (unsigned long long)((ts).w + 1u));     \
-            accPart[lane] = 0ull; accPart[kWave + lane] = 0ull; accPart[2 * kWave + lane] = 0ull;   \
-        } else {                                                                                  \
-            addBlock(acc_, sum, (ts).w + 1u, kargs()->measureCost != 0);                          \
-        }                                                                                         \
+        addBlock(acc_, sum, (ts).w + 1u, kargs()->measureCost != 0);                              \
         needTask = true;                                                                          \
     } while (0)
-    // Sample mode, tasks of several blocks: a block that is not the task's last one closes into the
-    // lane's LDS partial (exact 64-bit additions), and the next block's sum starts from zero.
-#define PT_CLOSE_BLOCK(y_)                                                                          \
-    do {                                                                                          \
-        const auto& Q_ = *kargs();                                                                \
-        if (GROUPS && Q_.group > 1 && (Q_.blockShift >= 0 ? ((y_) & (((uint32_t)1 << Q_.blockShift) - 1u)) == 0u \
-                                                 : (y_) % (uint32_t)Q_.block == 0u)) {            \
-            __hip_atomic_fetch_add(&accPart[lane], blockFixed(sum.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-            __hip_atomic_fetch_add(&accPart[kWave + lane], blockFixed(sum.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-            __hip_atomic_fetch_add(&accPart[2 * kWave + lane], blockFixed(sum.z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-            sum = f3(0.0f, 0.0f, 0.0f);                                                           \
-        }                                                                                         \
-    } while (0)
+    // New camera sample: main.cu:284-286 + camera::get_ray (lens sample: lensOffset; time draw skipped).
 #define PT_NEW_PATH()                                                                               \
     do {                                                                                          \
         const auto& Q_ = *kargs();                                                                \
@@ -1833,31 +1571,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                         PT_NEW_PATH();
                         sum = add(sum, sky(d, att));
                         ts.y++;
-                        if (ts.y < ts.z) PT_CLOSE_BLOCK(ts.y);
+                        if (ts.y < ts.z) (void)kargs();   // (see the SHADE step's note on this read)
                     }
                     PT_FINISH_TASK(ts);
                 }
             }
             needTask = false;
             waveReduceAdd(P.counters + 4, depthPaths);   // (paths counted per lane here)
-        }
-    } else if (CQ) {
-        if (P.max_depth <= 0) {   // (no bounce: every sample is its camera ray's sky colour)
-            for (;;) {
-                bool got = false;
-                PT_TAKE_PIXELS(got);
-                if (__ballot(got) == 0) break;
-                if (got) {
-                    for (; sample < nSamples; sample++) {
-                        PT_NEW_PATH();
-                        sum = add(sum, sky(d, att));
-                    }
-                    depthPaths += (uint32_t)nSamples;
-                    PT_FINISH_PIXEL();
-                }
-            }
-            needTask = false;
-            waveReduceAdd(P.counters + 4, depthPaths);
         }
     } else if (valid) {
         if (P.max_depth <= 0) {
@@ -1880,13 +1600,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #ifdef PT_DIAG
         const unsigned long long tH0 = __builtin_amdgcn_s_memtime();
 #endif
-        // binary: room for both children's leaves; wide: a node (the step handles a full queue)
-        // or a stack top waiting for queue space (node == -2)
-        // binary: room for both children's leaves in the queue; wide: no primitives pending
-        // (instanced: a lane with primitives waiting visits only siblings of its group -- the same
-        // object space; it pops, and may cross an instance marker, only with none waiting)
+        // binary: room for both children's leaves in the queue; wide: nodes left, and no primitives
+        // pending or (speculative traversal) room to park them.  Instanced kernels never park
+        // (SPEC is false there), so their second term is constant false; it stays because the
+        // compiler lays the step selection out around it: without it the instanced kernels come
+        // out 10 instructions shorter with other register assignments, a change to measure first.
         const bool wantNode = WIDE ? (INST ? ((tg == 0u && ((ng & 0xffu) != 0u || sp > 0)) ||
-                                              (SPEC && tg != 0u && ((oct >> 4) & 3u) < (uint32_t)SPECN && (ng & 0xffu) != 0u))
+                                              (SPEC && tg != 0u && (ng & 0xffu) != 0u))
                                            : ((SPEC ? (tg == 0u || ((oct >> 4) & 3u) < (uint32_t)SPECN) : tg == 0u) &&
                                               ((ng & 0xffu) != 0u || sp > 0)))
                                    : (node >= 0 && qn <= LQ - 2);
@@ -1917,13 +1637,6 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             }
             if constexpr (INST) {
                 if (wantNode) {
-                    if (SPEC && tg != 0u) {   // park the waiting primitive group (a sibling follows: same space)
-                        const uint32_t c = SPECN == 1 ? 0u : (oct >> 4) & 3u;
-                        pend[(2u * c) * kWave + lane] = tgBase;
-                        pend[(2u * c + 1u) * kWave + lane] = tg;
-                        oct += 16u;
-                    }
-                    if constexpr (SPEC) asm volatile("" ::: "memory");
                     // pop to a group with children left; a marker returns the lane to the world
                     // (oct bit 3: the instance transformed the direction, not only the origin)
                     while ((ng & 0xffu) == 0u && sp > 0) {
@@ -1983,12 +1696,6 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                         ng = (n1.x << 8) | (hits >> 24);
                         tgBase = n1.y;
                         tg = hits & 0xffffffu;
-                        if (SPEC && tg == 0u && (oct & 48u)) {   // no new primitives: the last parked group is current again
-                            oct -= 16u;
-                            const uint32_t c = SPECN == 1 ? 0u : (oct >> 4) & 3u;
-                            tgBase = pend[(2u * c) * kWave + lane];
-                            tg = pend[(2u * c + 1u) * kWave + lane];
-                        }
                     }
                 }
             } else if constexpr (WIDE) {
@@ -2095,83 +1802,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             // ------------------------------------------------------------------ LEAF
             bool tested = false, sph = false;
             PT_DIAG_ADD(itL, 1u);
-            if constexpr (COOP) {
-                // Wave-cooperative LEAF step: the waiting (lane, primitive) pairs are compacted
-                // so that every lane of the wave tests one.  A lane offers the first `cnt` (<= CAP)
-                // primitives of its group in group order; a ballot prefix sum over the lanes gives
-                // each offer its queue slot (the first 64 slots are taken, the rest wait for the
-                // next LEAF step); lane j tests the pair in slot j against its owner's ray (fetched
-                // with ds_bpermute) and hands (t, leaf box, key) back; each owner then merges its
-                // results in group order with wideMerge -- the decisions wideTest makes, in the same
-                // order, so closest / best / window / redo are exactly those of the one-lane tests.
-                constexpr uint32_t CAP = PT_LEAF_COOP_CAP;
-                const uint32_t pc = (uint32_t)__builtin_popcount(tg);
-                const uint32_t cnt = pc < CAP ? pc : CAP;
-                const uint64_t c0 = __ballot(cnt & 1u), c1 = __ballot(cnt & 2u);
-                const uint32_t pre = mbcnt64(c0) + 2u * mbcnt64(c1);
-                const uint32_t total = (uint32_t)__popcll(c0) + 2u * (uint32_t)__popcll(c1);   // (uniform)
-                const uint32_t take = pre >= (uint32_t)kWave ? 0u : min(cnt, (uint32_t)kWave - pre);
-                const uint32_t own = (uint32_t)lane << 26;   // slot entry: owner << 26 | primitive (< 2^26)
-                if (take > 0u) { leafQ[pre] = own | (tgBase + (uint32_t)__builtin_ctz(tg)); tg &= tg - 1u; }
-                if (CAP > 1 && take > 1u) { leafQ[pre + 1u] = own | (tgBase + (uint32_t)__builtin_ctz(tg)); tg &= tg - 1u; }
-                if (CAP > 2 && take > 2u) { leafQ[pre + 2u] = own | (tgBase + (uint32_t)__builtin_ctz(tg)); tg &= tg - 1u; }
-                __syncthreads();   // (one wave per workgroup: orders the slot writes before the reads)
-                const uint32_t nc = total < (uint32_t)kWave ? total : (uint32_t)kWave;
-                PT_DIAG_ADD(sPops, nc);
-                // lanes past the last pair re-test a stale (valid) entry; their results are not read
-                const uint32_t e = leafQ[lane];
-                const int ow = (int)(e >> 26);
-                const float3 ro = f3(__shfl(o.x, ow), __shfl(o.y, ow), __shfl(o.z, ow));
-                const float3 rd = f3(__shfl(d.x, ow), __shfl(d.y, ow), __shfl(d.z, ow));
-                const float4* w0 = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(S.wprims) + mul48(e & 0x3ffffffu));
-                const Prim q0{w0[0], w0[1], w0[2]};
-                const bool lb = S.nprims > 1;
-                const bool cons = (uint32_t)lane < nc;
-                float rt, rlo = -__builtin_inff();
-                uint32_t rkey;
-                if (kargs()->S.hasSpheres) {   // (uniform)
-                    const bool sph = __float_as_uint(q0.p2.w) != 0u;
-                    rt = primHitAny(q0, sph, ro, rd, 0.001f);
-                    if (lb) {
-                        const float3 rinv = f3(__shfl(inv.x, ow), __shfl(inv.y, ow), __shfl(inv.z, ow));
-                        const SlabHit b = refLeafBox(q0, sph, ro, rinv, 0.001f, __builtin_inff());
-                        rlo = b.hit ? b.lo : -1.0f;   // (a hit's entry is >= tmin > 0)
-                    }
-                    rkey = __float_as_uint(q0.p0.w) | (sph ? kSphereBit : 0u);
-                    sTris += (uint32_t)__popcll(__ballot(cons && !sph));
-                    sSph += (uint32_t)__popcll(__ballot(cons && sph));
-                } else {
-                    rt = primHitAny(q0, false, ro, rd, 0.001f);
-                    if (lb) {
-                        const float3 rinv = f3(__shfl(inv.x, ow), __shfl(inv.y, ow), __shfl(inv.z, ow));
-                        const SlabHit b = refLeafBox(q0, false, ro, rinv, 0.001f, __builtin_inff());
-                        rlo = b.hit ? b.lo : -1.0f;
-                    }
-                    rkey = __float_as_uint(q0.p0.w);
-                    sTris += nc;
-                }
-                bool redo = false;
-                const bool sphScene = kargs()->S.hasSpheres != 0;
-#pragma unroll
-                for (uint32_t r = 0; r < CAP; r++) {
-                    if (__ballot(take > r) == 0) break;
-                    const int src = (int)(pre + r);
-                    const float t = __shfl(rt, src);
-                    const float blo = __shfl(rlo, src);
-                    const uint32_t key = (uint32_t)__shfl((int)rkey, src);
-                    if (take > r) {
-                        if (sphScene) wideMerge<true>(t, key, blo, closest, best, bestLo, lb, redo);
-                        else wideMerge<false>(t, key, blo, closest, best, bestLo, lb, redo);
-                    }
-                }
-                if (redo) oct |= 8u;   // order-dependent candidate: repeat the query in the reference's order
-                if (SPEC && tg == 0u && (oct & 48u)) {   // this group is done: the last parked one is next
-                    oct -= 16u;
-                    const uint32_t c = SPECN == 1 ? 0u : (oct >> 4) & 3u;
-                    tgBase = pend[(2u * c) * kWave + lane];
-                    tg = pend[(2u * c + 1u) * kWave + lane];
-                }
-            } else if constexpr (WIDE) {
+            if constexpr (WIDE) {
                 PT_DIAG_ADD(sPops, (uint32_t)nL);
                 // up to two primitives of the group per step, both records loaded up front
                 uint32_t k0 = 0u, k1 = 0u;
@@ -2311,14 +1942,16 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                             active = false;
                             PT_FINISH_TASK(ts);
                         } else {
-                            PT_CLOSE_BLOCK(ts.y);
+                            // A kernarg pointer re-read with no user (kargs' empty asm is volatile):
+                            // without it the sample kernels come out 12 instructions shorter with
+                            // other register assignments, a change to measure before it is made.
+                            (void)kargs();
                             newSample = true;
                         }
                     } else {
                         ++sample;
                         if (sample == nSamples) {
                             active = false;
-                            if constexpr (CQ) PT_FINISH_PIXEL();
                         } else {
                             newSample = true;
                         }
@@ -2333,13 +1966,6 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             if constexpr (SAMPLE) {   // idle lanes take new tasks and start their first path
                 bool got = false;
                 PT_TAKE_TASKS(got);
-                if (got) {
-                    active = true;
-                    newRay = newSample = true;
-                }
-            } else if constexpr (CQ) {   // idle lanes take new pixels and start their first sample
-                bool got = false;
-                PT_TAKE_PIXELS(got);
                 if (got) {
                     active = true;
                     newRay = newSample = true;
@@ -2370,7 +1996,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         }
 #endif
     }
-    if constexpr (!SAMPLE && !CQ) {   // (sample mode / CQ: every task wrote its result when it ended)
+    if constexpr (!SAMPLE) {   // (sample mode: every task wrote its result when it ended)
         if (valid) {
             storePixel(P, idx, sum);
             P.sd[idx] = g.d; P.s0[idx] = g.v0; P.s1[idx] = g.v1; P.s2[idx] = g.v2; P.s3[idx] = g.v3; P.s4[idx] = g.v4;
@@ -2378,14 +2004,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         }
     }
     const unsigned long long tEnd = __builtin_amdgcn_s_memrealtime();
-#if PT_AB_COST_STORE
-    if (!SAMPLE && !CQ && !crit && lane == 0) P.tileCost[tile] = (unsigned)min(tEnd - tStart, 0xffffffffull);
-#else
-    if (!SAMPLE && !CQ && !crit && lane == 0) atomicMax(P.tileCost + tile, (unsigned)min(tEnd - tStart, 0xffffffffull));   // (split tiles: several waves)
-#endif
-    if constexpr (SAMPLE) {   // max_depth <= 0: paths counted per lane
-
-    }
+    if (!SAMPLE && !crit && lane == 0) atomicMax(P.tileCost + tile, (unsigned)min(tEnd - tStart, 0xffffffffull));   // (split tiles: several waves)
     if (P.waveTimes && lane == 0) {
         unsigned xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
@@ -2428,9 +2047,6 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #undef PT_NEW_PATH
 #undef PT_TAKE_TASKS
 #undef PT_FINISH_TASK
-#undef PT_TAKE_PIXELS
-#undef PT_FINISH_PIXEL
-#undef PT_CLOSE_BLOCK
 #undef PT_DIAG_ADD
 
 #ifdef PT_TU_COMPAT
@@ -2444,7 +2060,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 namespace pt {
 int launchCompatWide(int stack, const void* params, hipStream_t st) {
     const RenderParams& P = *static_cast<const RenderParams*>(params);
-    const int grid = PT_COMPAT_QUEUE ? P.nwaves : P.compatGrid;   // persistent waves with the pixel queue
+    const int grid = P.compatGrid;
     switch (stack) {
         case 8: renderKernelWF<8, false, true><<<grid, kWave, 0, st>>>(P); break;
         case 16: renderKernelWF<16, false, true><<<grid, kWave, 0, st>>>(P); break;
@@ -3410,11 +3026,7 @@ struct StreamGuard {
 
 int stackFor(int depth) {
     const int need = depth + 1;
-#if PT_STACK24
     for (int s : {16, 24, 32, 48, 64, 80})
-#else
-    for (int s : {16, 32, 48, 64, 80})
-#endif
         if (need <= s) return s;
     return -1;
 }
@@ -3961,7 +3573,7 @@ template <int S>
 void launchRenderWide(const RenderParams& P, hipStream_t st) {
     if (P.S.winst) {   // an instanced scene's two-level tree
         if (P.pixAcc) renderKernelWF<S, true, true, true><<<P.nwaves, kWave, 0, st>>>(P);
-        else renderKernelWF<S, false, true, true><<<PT_COMPAT_QUEUE ? P.nwaves : P.compatGrid, kWave, 0, st>>>(P);
+        else renderKernelWF<S, false, true, true><<<P.compatGrid, kWave, 0, st>>>(P);
         return;
     }
     if (P.pixAcc) renderKernelWF<S, true, true><<<P.nwaves, kWave, 0, st>>>(P);
@@ -3972,7 +3584,7 @@ void launchRender(const RenderParams& P, hipStream_t st) {
     if (P.kernel == PT_KERNEL_WAVEFRONT && P.pixAcc)
         renderKernelWF<S, true, false><<<P.nwaves, kWave, 0, st>>>(P);
     else if (P.kernel == PT_KERNEL_WAVEFRONT)
-        renderKernelWF<S, false, false><<<PT_COMPAT_QUEUE ? P.nwaves : P.compatGrid, kWave, 0, st>>>(P);
+        renderKernelWF<S, false, false><<<P.compatGrid, kWave, 0, st>>>(P);
     else if (P.pixAcc) renderKernel<S, true><<<P.ntiles, kWave, 0, st>>>(P);
     else renderKernel<S, false><<<P.ntiles, kWave, 0, st>>>(P);
 }
@@ -3982,8 +3594,9 @@ int wavesPerCU(int& n) {
                                                          kWave, 0));
     return PT_OK;
 }
-// Persistent waves per CU of the render kernel a launch runs (sample mode, or compat mode with the
-// pixel queue): its occupancy.  The compat wide kernels live in pt_compat.hip's translation unit.
+// Waves per CU of the render kernel a launch runs: its occupancy (sample mode launches exactly the
+// waves that fit; compat launches do not ask).  The compat wide kernels live in pt_compat.hip's
+// translation unit.
 int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample) {
     if (kernel == PT_KERNEL_WIDE && inst) {
         switch (stack) {
@@ -4004,9 +3617,7 @@ int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample) 
     }
     switch (stack) {
         case 16: return sample ? wavesPerCU<16, false>(n) : wavesPerCU<16, false, false, false>(n);
-#if PT_STACK24
         case 24: return sample ? wavesPerCU<24, false>(n) : wavesPerCU<24, false, false, false>(n);
-#endif
         case 32: return sample ? wavesPerCU<32, false>(n) : wavesPerCU<32, false, false, false>(n);
         case 48: return sample ? wavesPerCU<48, false>(n) : wavesPerCU<48, false, false, false>(n);
         case 64: return sample ? wavesPerCU<64, false>(n) : wavesPerCU<64, false, false, false>(n);
@@ -4027,9 +3638,7 @@ int dispatchRender(int stack, const RenderParams& P, hipStream_t st) {
     }
     switch (stack) {
         case 16: launchRender<16>(P, st); break;
-#if PT_STACK24
         case 24: launchRender<24>(P, st); break;
-#endif
         case 32: launchRender<32>(P, st); break;
         case 48: launchRender<48>(P, st); break;
         case 64: launchRender<64>(P, st); break;
@@ -4061,9 +3670,7 @@ int dispatchTrace(int stack, bool wide, const DevScene& S, const pt_ray* r, int6
         } else {
             switch (stack) {
                 case 16: traceKernelQ<16><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-#if PT_STACK24
                 case 24: traceKernelQ<24><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-#endif
                 case 32: traceKernelQ<32><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
                 case 48: traceKernelQ<48><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
                 case 64: traceKernelQ<64><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
@@ -4096,9 +3703,7 @@ int dispatchTrace(int stack, bool wide, const DevScene& S, const pt_ray* r, int6
     }
     switch (stack) {
         case 16: traceKernel<16><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-#if PT_STACK24
         case 24: traceKernel<24><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-#endif
         case 32: traceKernel<32><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
         case 48: traceKernel<48><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
         case 64: traceKernel<64><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
@@ -4850,14 +4455,12 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     }
     const bool lpt = !(opts && (opts->flags & PT_RENDER_IDENTITY_ORDER));
     const bool sample = rng == PT_RNG_SAMPLE && np > 0 && P.ntiles > 0;
-    // compat mode, pixel queue (renderKernelWF, PT_COMPAT_QUEUE): persistent waves take pixels
-    const bool cq = PT_COMPAT_QUEUE && !sample && kernel != PT_KERNEL_SIMPLE && np > 0 && P.ntiles > 0;
     if (!f->cus) {
         if (hipDeviceGetAttribute(&f->cus, hipDeviceAttributeMultiprocessorCount, f->device) != hipSuccess)
             f->cus = 256;
         f->cus = std::max(f->cus, 1);
     }
-    // persistent waves (sample mode, CQ): exactly the waves that fit at once -- the kernel's
+    // persistent waves (sample mode): exactly the waves that fit at once -- the kernel's
     // occupancy per CU, which the LDS stack caps on deep trees.  Queried once per (device, kernel
     // instantiation) and process.
     auto perCUFor = [&](int& perCU) -> int {
@@ -4886,7 +4489,7 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     P.critList = nullptr;
     P.critFlag = nullptr;
     P.pixRays = nullptr;
-    const bool critOn = lpt && critFor(sample, kernel == PT_KERNEL_WIDE, s->instanced, cq, stack) && np > 0 &&
+    const bool critOn = lpt && critFor(sample, kernel == PT_KERNEL_WIDE, s->instanced, stack) && np > 0 &&
                         max_depth > 16 && envCount("PT_CRIT_PIXELS", kCritPixels) > 0;
     if (critOn) {
         if ((rc = devReserve(f->pixRays, (size_t)np * 4))) return rc;
@@ -4905,39 +4508,21 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     // Short-path frames are throughput-bound and the split's idle lanes cost (C5, depth 16: 548 ->
     // 553 ms; C2, depth 8: +0.9 %).
     P.splitWays = std::max(1, std::min(8, envCount("PT_SPLIT_WAYS", 2)));
-    P.splitTiles = (lpt && f->haveOrder && !sample && !cq && kernel != PT_KERNEL_SIMPLE)
+    P.splitTiles = (lpt && f->haveOrder && !sample && kernel != PT_KERNEL_SIMPLE)
                        ? std::max(0, std::min(P.ntiles, envCount("PT_SPLIT_TILES", max_depth > 16 && !critOn ? 128 : 0))) : 0;
-    if (P.splitWays == 1 || PT_AB_NO_SPLIT) P.splitTiles = 0;   // (a build without the split prologue: grid = tiles)
+    if (P.splitWays == 1) P.splitTiles = 0;
     P.compatGrid = P.critWaves + P.ntiles + P.splitTiles * (P.splitWays - 1);
     // diagnostic: only the first k waves of the launch order (the longest tiles) -- their chains'
     // latency with the machine otherwise idle; the other pixels are not rendered
     if (const int lim = envCount("PT_COMPAT_GRID_LIMIT", 0)) P.compatGrid = std::min(P.compatGrid, lim);
-    if (cq) {
-        P.ntasks = (uint32_t)P.ntiles * 64u;   // queue slots: tile slot x 64 pixels
-        if (!f->taskCounter.p && (rc = devAlloc(f->taskCounter, 64))) return rc;
-        HIP_TRY(hipMemsetAsync(f->taskCounter.p, 0, 4, st));
-        P.taskCounter = f->taskCounter.as<unsigned>();
-        int perCU = 0;
-        if ((rc = perCUFor(perCU))) return rc;
-        P.nwaves = (int)std::min<uint64_t>((uint64_t)f->cus * (uint64_t)std::max(1, perCU) * (uint64_t)envInt("PT_CQ_WAVES_MULT", 1),
-                                           (uint64_t)P.ntiles);
-        if (std::getenv("PT_ITER_STATS"))
-            std::fprintf(stderr, "[pt] compat pixel queue: persistent waves %d (%d per CU, stack %d)\n", P.nwaves, perCU, stack);
-        // tile costs (the rays of the tile's longest pixel, atomicMax per pixel) on every launch
-        P.measureCost = lpt ? 1 : 0;
-        if (P.measureCost) HIP_TRY(hipMemsetAsync(f->tileCost.p, 0, ntl * 4, st));
-    }
     if (sample) {
         if (f->width >= 65536 || f->nrows >= 65536)
             return fail(PT_ERR_INVALID, "sample mode: frame width and rows must be < 65536");
         P.block = (opts && opts->chunk > 0) ? opts->chunk : std::max(16, (spp + 63) / 64);
         P.nblocks = (spp + P.block - 1) / P.block;
         P.blockShift = (P.block & (P.block - 1)) == 0 ? __builtin_ctz((unsigned)P.block) : -1;
-        // blocks per task (the simple kernel always takes one)
-        P.group = (!PT_TASK_GROUPS || kernel != PT_KERNEL_WIDE || stack > 16) ? 1   // (renderKernelWF's GROUPS)
-                                                          : std::max(1, std::min(P.nblocks, envInt("PT_TASK_BLOCKS", kTaskBlocks)));
-        P.span = P.group * P.block;
-        P.ngroups = (spp + P.span - 1) / P.span;
+        P.span = P.block;   // one summation block per task
+        P.ngroups = P.nblocks;
         if ((rc = devReserve(f->pixAcc, (size_t)np * 32))) return rc;   // {x, y, z, rays} per pixel
         HIP_TRY(hipMemsetAsync(f->pixAcc.p, 0, (size_t)np * 32, st));
         P.pixAcc = f->pixAcc.as<unsigned long long>();
@@ -4945,14 +4530,8 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
         if (ntasks >= (1ull << 32) - 4096)
             return fail(PT_ERR_INVALID, "sample mode: too many (pixel, block) tasks; raise the block size (chunk)");
         P.ntasks = (uint32_t)ntasks;
-        if (PT_XCD_POOLS && ntasks >= (1ull << 28))
-            return fail(PT_ERR_INVALID, "sample mode with XCD pools: too many tasks; raise the block size (chunk)");
         if (!f->taskCounter.p && (rc = devAlloc(f->taskCounter, 64))) return rc;
-#if PT_XCD_POOLS
-        HIP_TRY(hipMemsetAsync(f->taskCounter.p, 0, 32, st));   // the eight XCD counters
-#else
         HIP_TRY(hipMemsetAsync(f->taskCounter.p, 0, 4, st));
-#endif
         P.taskCounter = f->taskCounter.as<unsigned>();
         int perCU = 0;
         if ((rc = perCUFor(perCU))) return rc;
@@ -4970,7 +4549,7 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     // Deep trees: stack entries beyond kLdsStack live in memory, per wave slot (persistent wave or
     // compat tile) and lane
     if (kernel == PT_KERNEL_WAVEFRONT && stack > PT_LDS_STACK && P.ntiles > 0) {
-        const size_t slots = (sample || cq) ? (size_t)P.nwaves : (size_t)P.compatGrid;
+        const size_t slots = sample ? (size_t)P.nwaves : (size_t)P.compatGrid;
         if ((rc = devReserve(f->stackSpill, slots * kWave * (size_t)(stack - PT_LDS_STACK) * 4))) return rc;
         P.stackSpill = f->stackSpill.as<uint32_t>();
     }
@@ -4994,8 +4573,8 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     P.tileOrder = (lpt && f->haveOrder) ? f->tileOrder.as<int>() : nullptr;
     P.tileXY = nullptr;
     P.nblocksShift = -1;
-    if (sample || cq) {   // the launch order decoded per slot (tileXYKernel; the ordered table follows each sort)
-        if (sample) P.nblocksShift = (P.ngroups & (P.ngroups - 1)) == 0 ? __builtin_ctz((unsigned)P.ngroups) : -1;
+    if (sample) {   // the launch order decoded per slot (tileXYKernel; the ordered table follows each sort)
+        P.nblocksShift = (P.ngroups & (P.ngroups - 1)) == 0 ? __builtin_ctz((unsigned)P.ngroups) : -1;
         if (!P.tileOrder && !f->haveXYId) {
             tileXYKernel<<<(unsigned)((ntl + 255) / 256), 256, 0, st>>>(nullptr, (int)ntl, P.tiles_x, f->tileXYId.as<uint32_t>());
             HIP_TRY(hipGetLastError());
@@ -5003,14 +4582,14 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
         }
         P.tileXY = P.tileOrder ? f->tileXY.as<uint32_t>() : f->tileXYId.as<uint32_t>();
     }
-    P.prioTiles = (P.tileOrder && !sample && !cq) ? envCount("PT_PRIO_TILES", 1024) : 0;
+    P.prioTiles = (P.tileOrder && !sample) ? envCount("PT_PRIO_TILES", 1024) : 0;
     P.prioLevel = std::max(1, std::min(3, envCount("PT_PRIO_LEVEL", 2)));
-    if (!sample && !cq && kernel != PT_KERNEL_SIMPLE && P.ntiles > 0)   // (tile costs: atomicMax of the tile's waves)
+    if (!sample && kernel != PT_KERNEL_SIMPLE && P.ntiles > 0)   // (tile costs: atomicMax of the tile's waves)
         HIP_TRY(hipMemsetAsync(f->tileCost.p, 0, ntl * 4, st));
     DevBuf dtimes;
     const char* timesPath = std::getenv("PT_WAVE_TIMES");   // diagnostic: per-wave timestamps
     P.waveTimes = nullptr;
-    const size_t nwaves = (sample || (cq && kernel != PT_KERNEL_SIMPLE)) ? (size_t)P.nwaves
+    const size_t nwaves = sample ? (size_t)P.nwaves
                         : (kernel != PT_KERNEL_SIMPLE ? (size_t)std::max(1, P.compatGrid) : ntl);   // = grid size
     if (timesPath && *timesPath && kernel != PT_KERNEL_SIMPLE) {
         if ((rc = devAlloc(dtimes, nwaves * 24))) return rc;

@@ -19,6 +19,26 @@ constexpr int kW8NodeDwords = PT_NODE_DWORDS;   // node slot in dwords: 80-B rec
 static_assert(kW8NodeDwords == 20 || kW8NodeDwords == 32, "node slots of 80 or 128 B");
 constexpr int kW8PrimDwords = 12;   // 48-B primitive record
 
+// The builders' smallest plane quantum is 2^-kW8EminShift of the larger of the scene's extent and
+// its coordinates; the traversal sends a ray whose origin lies farther than kW8FarExt scene extents
+// from the scene's centre to the reference-order query instead of the quantised test (wideFar,
+// pt_device.hip).  The two move together: the planes' outward margin (>= 2^-shift of the scale)
+// must stay beyond the rounding of the ray's plane distances (about 2^-21.6 of |p - o|), which
+// grows with the far line.  The bound below restates that argument (the wideHits comment) at the
+// shipped pair, shift 18 with 8 extents -- it is no new measurement: a finer quantum needs a
+// nearer far line by the same factor.
+#ifndef PT_WIDE_EMIN_SHIFT
+#define PT_WIDE_EMIN_SHIFT 18
+#endif
+#ifndef PT_WIDE_FAR_EXT
+#define PT_WIDE_FAR_EXT 8.0f
+#endif
+constexpr int kW8EminShift = PT_WIDE_EMIN_SHIFT;
+constexpr float kW8FarExt = PT_WIDE_FAR_EXT;
+static_assert(kW8EminShift >= 0 && kW8EminShift < 31 &&
+                  (double)kW8FarExt * (double)(1u << kW8EminShift) <= 8.0 * (double)(1u << 18),
+              "PT_WIDE_EMIN_SHIFT and PT_WIDE_FAR_EXT move together: far line * 2^shift <= 8 * 2^18");
+
 struct Wide8 {
     std::vector<uint32_t> nodes;   // kW8NodeDwords per node slot; slot 0 = root
     std::vector<uint32_t> prims;   // kW8PrimDwords per primitive, in traversal (leaf) order

@@ -226,7 +226,7 @@ int main(int argc, char** argv) {
     }
     P = w.prims.data();
     N = w.nodes.data();
-    // 1. structure.  The smallest quantum, as the builder takes it: 2^-18 of the larger of the
+    // 1. structure.  The smallest quantum, as the builder takes it: 2^-kW8EminShift (pt_wide8.hpp) of the larger of the
     // scene's extent and coordinates (rounded up to a power of two)
     double ext = 0.0;
     {
@@ -238,7 +238,7 @@ int main(int argc, char** argv) {
             }
         for (int a = 0; a < 3; a++) ext = std::fmax(ext, std::fmax(std::fmax(std::fabs(mn[a]), std::fabs(mx[a])), mx[a] - mn[a]));
     }
-    const int emin = ext > 0.0 ? std::max(-100, (int)std::ceil(std::log2(ext)) - 18) : -100;
+    const int emin = ext > 0.0 ? std::max(-100, (int)std::ceil(std::log2(ext)) - pt::kW8EminShift) : -100;
     const double minQuantum = std::ldexp(1.0, emin);
     std::vector<int> seen((size_t)n, 0);
     std::vector<int> kOfRank((size_t)n, -1);
