@@ -203,6 +203,24 @@ int pt_trace_closest_ex(pt_scene* scene, const pt_ray* rays, int64_t n, float tm
  * pointers, traced on `stream` (a hipStream_t, may be NULL); returns when the batch is done. */
 int pt_trace_closest_device(pt_scene* scene, const pt_ray* rays, int64_t n, float tmin, float tmax, int kernel,
                             pt_hit* hits, void* stream, pt_stats* stats);
+/* Visibility ("any hit") queries: occluded[i] = 1 when ray i meets any primitive with t in the
+ * closest-hit query's interval, else 0 -- exactly pt_trace_closest_ex's hit flag for that ray
+ * (same scene, tmin and tmax; so a triangle at exactly t == tmax does not occlude and a sphere
+ * root at exactly tmax does), found without the hit record and without walking on after the
+ * first blocker.  ray_tmax, when not NULL, gives each ray its own tmax (shadow rays: the distance
+ * to the light) and the scalar tmax is ignored.  kernel: PT_KERNEL_DEFAULT and PT_KERNEL_WIDE
+ * traverse the compressed 8-wide tree (built at first use; the answer has no order to honour, so
+ * the fast tree is the default), PT_KERNEL_SIMPLE / PT_KERNEL_WAVEFRONT the binary LBVH in the
+ * reference's order (PT_ERR_INVALID on an instanced scene).  rays / ray_tmax / occluded are host
+ * pointers; stats counts the work done up to each ray's first blocker. */
+int pt_trace_occluded(pt_scene* scene, const pt_ray* rays, int64_t n, float tmin, float tmax,
+                      const float* ray_tmax, int kernel, uint8_t* occluded, pt_stats* stats);
+/* pt_trace_occluded on device-resident arrays (e.g. torch tensors): rays / ray_tmax / occluded are
+ * device pointers (n rays, n floats or NULL, n bytes), traced on `stream` (a hipStream_t, may be
+ * NULL); exactly n bytes are written; returns when the batch is done. */
+int pt_trace_occluded_device(pt_scene* scene, const pt_ray* rays, int64_t n, float tmin, float tmax,
+                             const float* ray_tmax, int kernel, uint8_t* occluded, void* stream,
+                             pt_stats* stats);
 /* Per-pixel XORWOW streams, initRandom (main.cu:262-269): curand_init(seed, pixel, 0, ...)
  * for every pixel of the rows this film owns.  Rows are grouped in stripes of stripe_height;
  * stripe s belongs to part (s % n_parts).  n_parts = 1 owns the whole frame. */

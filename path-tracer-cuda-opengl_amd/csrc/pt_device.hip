@@ -2624,6 +2624,232 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_
     waveReduceAdd(counters + 3, c.spheres);
 }
 
+// ------------------------------------------------------------------------ occlusion (any hit)
+// pt_trace_occluded: occ[i] = 1 exactly when the closest-hit query of ray i over [tmin, tmax_i]
+// reports a hit (DESIGN.md "Occlusion queries").  The reference's traversal accepts a hit iff some
+// primitive P passes (a) primHitT(P, o, d, tmin, tmax) >= 0 and (b) the scene has one primitive,
+// or P's exact leaf box passes the slab test over [tmin, tmax] (refLeafBox): `closest` only
+// shrinks once a hit exists, ancestor boxes contain the leaf box (monotonic slab arithmetic,
+// traceRefStackless) and the wide planes never reject a box the exact test accepts (wideHits).
+// So the walk keeps the interval fixed and stops at the first primitive that passes (a) and (b):
+// the closest-hit kernels' walk up to their first accepted hit, hence never more work.
+// rayTmax (optional): per-ray tmax, replacing the scalar.
+
+// One primitive test of the fixed interval, counted as primTest counts it.
+__device__ __forceinline__ bool primTestAny(const DevScene& S, uint32_t ref, float3 o, float3 d, float tmin, float tmax,
+                                            Counters& c) {
+    const bool sph = (ref & kSphereBit) != 0;
+    if (sph) c.spheres++;
+    else c.tris++;
+    return primHitT(loadPrim(S, ref & kPrimMask), sph, o, d, tmin, tmax) >= 0.0f;
+}
+
+// pt_trace_occluded on the binary LBVH (PT_KERNEL_SIMPLE / PT_KERNEL_WAVEFRONT): traceKernelQ's walk
+// (the reference's visiting order, trace<STACK>, with the ray queue) with the interval fixed at the
+// ray's tmax; a lane stops at the first accepted primitive and takes the next ray.
+template <int STACK>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_WAVES))) void occludedKernelQ(
+    DevScene S, const pt_ray* rays, int64_t n, float tmin, float tmax, const float* __restrict__ rayTmax, uint8_t* occ,
+    unsigned long long* counters) {
+    __shared__ uint32_t stk[STACK * kWave];
+    const int lane = threadIdx.x;
+    uint32_t* my = stk + lane;
+    Counters c{0, 0, 0, 0};
+    int64_t ray = -1, poolBase = 0;
+    uint32_t poolLeft = 0u;
+    bool more = true;
+    float3 o = f3(0.0f, 0.0f, 0.0f), d = o, inv = o;
+    float tmaxR = 0.0f;
+    int node = 0, sp = 0, guard = 0;
+    for (;;) {
+        bool took = false;
+        PT_TRACE_REFILL(took);
+        if (__ballot(ray >= 0) == 0) break;
+        if (ray < 0) continue;
+        bool fin = false, hit = false;
+        if (took) {   // the query's start (trace<STACK>)
+            const pt_ray r = rays[ray];
+            o = f3(r.o[0], r.o[1], r.o[2]);
+            d = f3(r.d[0], r.d[1], r.d[2]);
+            tmaxR = rayTmax ? rayTmax[ray] : tmax;
+            c.rays++;
+            if (S.nprims <= 1) {
+                if (S.nprims == 1)   // root is a leaf: tested without a box test (:92-98)
+                    hit = primTestAny(S, kLeafBit | (__float_as_uint(S.prims[2].w) ? kSphereBit : 0u), o, d, tmin, tmaxR, c);
+                fin = true;
+            } else {
+                inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));
+                node = 0;
+                sp = 0;
+                guard = 0;
+            }
+        }
+        if (!fin) {   // one node visit of trace<STACK>
+            if (++guard > S.nprims) { atomicOr(S.err, 1u); fin = true; }
+            else {
+                c.visits++;
+                const float4* np = S.nodes + 4 * (size_t)node;
+                const float4 a = np[0], b = np[1], q = np[2], rr = np[3];
+                const uint32_t lref = __float_as_uint(rr.x), rref = __float_as_uint(rr.y);
+                if (slabLeft(a, b, o, inv, tmin, tmaxR).hit) {
+                    if (lref & kLeafBit) hit = primTestAny(S, lref, o, d, tmin, tmaxR, c);
+                    else if (sp < STACK) { my[sp * kWave] = lref; sp++; }
+                    else { atomicOr(S.err, 2u); fin = true; }
+                }
+                if (!fin && !hit && slabRight(b, q, o, inv, tmin, tmaxR).hit) {
+                    if (rref & kLeafBit) hit = primTestAny(S, rref, o, d, tmin, tmaxR, c);
+                    else if (sp < STACK) { my[sp * kWave] = rref; sp++; }
+                    else { atomicOr(S.err, 2u); fin = true; }
+                }
+                fin = fin || hit;
+                if (!fin) {
+                    if (sp == 0) fin = true;
+                    else { sp--; node = (int)my[sp * kWave]; }
+                }
+            }
+        }
+        if (fin) {
+            occ[ray] = hit ? 1 : 0;
+            ray = -1;
+        }
+    }
+    waveReduceAdd(counters + 0, c.rays);
+    waveReduceAdd(counters + 1, c.visits);
+    waveReduceAdd(counters + 2, c.tris);
+    waveReduceAdd(counters + 3, c.spheres);
+}
+
+// pt_trace_occluded on the wide tree: traceKernelWideQ's walk (ray queue, node loads, node tests,
+// nearest-first child order) with the interval fixed at the ray's tmax, one lane per ray; a lane
+// stops at the first primitive that passes the contract's test and takes the next ray.  A far
+// origin or a direction the MIX planes cannot take (wideFar, mixUnsafe) is answered by the
+// reference-order query's flag, as in the closest-hit kernel (no work counted there either).
+// INST: the two-level walk; no leaf boxes, so the test is (a) alone in the instance's space.
+template <int STACK, bool INST>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_WAVES))) void occludedKernelWideQ(
+    DevScene S, const pt_ray* rays, int64_t n, float tmin, float tmax, const float* __restrict__ rayTmax, uint8_t* occ,
+    unsigned long long* counters) {
+    __shared__ uint32_t stk[STACK * kWave];
+    const int lane = threadIdx.x;
+    uint32_t* my = stk + lane;
+    const __amdgpu_buffer_rsrc_t nodeRsrc = rawRsrc(S.wnodes);
+    Counters c{0, 0, 0, 0};
+    int64_t ray = -1, poolBase = 0;
+    uint32_t poolLeft = 0u;
+    bool more = true;
+    float3 wo2 = f3(0.0f, 0.0f, 0.0f), wd = wo2, winv = wo2, o = wo2, d = wo2, inv = wo2;
+    uint32_t woct = 0u, oct = 0u, ng = 0u, tgBase = 0u, tg = 0u;
+    float tminI = 0.0f, tmaxI = 0.0f;
+    int sp = 0;
+    for (;;) {
+        bool took = false;
+        PT_TRACE_REFILL(took);
+        if (__ballot(ray >= 0) == 0) break;
+        if (ray < 0) continue;
+        bool hit = false, fin = false;
+        if (took) {   // the query's start (traceKernelWideQ)
+            const pt_ray r = rays[ray];
+            const float3 wo = f3(r.o[0], r.o[1], r.o[2]);
+            const float tmaxR = rayTmax ? rayTmax[ray] : tmax;
+            wd = f3(r.d[0], r.d[1], r.d[2]);
+            winv = f3(rcpRN(wd.x), rcpRN(wd.y), rcpRN(wd.z));
+            woct = (winv.x < 0.0f ? 1u : 0u) | (winv.y < 0.0f ? 2u : 0u) | (winv.z < 0.0f ? 4u : 0u);
+            o = wo; d = wd; inv = winv;
+            oct = woct;
+            const bool far = !INST && (wideFar(S, o) || (PT_WIDE_MIX && mixUnsafe(winv, S.mixLim)));
+            wo2 = wo;
+            const float shift = (INST && instFar(S, wo)) ? instEntry(S.cx, S.cy, S.cz, S.ext, wo2, wd, winv) : 0.0f;
+            if (INST) o = wo2;
+            tminI = tmin - shift;
+            tmaxI = tmaxR - shift;
+            sp = 0;
+            ng = S.nprims > 0 && !far ? (1u << oct) : 0u;
+            tgBase = 0u;
+            tg = 0u;
+            c.rays++;
+            if (far) {   // the query in the reference's order: its flag
+                float closest = tmaxR;
+                hit = traceRefStackless(S, o, d, tmin, closest) >= 0;
+                fin = true;
+            }
+        }
+        while (tg && !hit) {
+            const uint32_t k = tgBase + (uint32_t)__builtin_ctz(tg);
+            tg &= tg - 1u;
+            const float4* w = S.wprims + 3 * (size_t)k;
+            const Prim q{w[0], w[1], w[2]};
+            const bool sph = __float_as_uint(q.p2.w) != 0u;
+            if (sph) c.spheres++;
+            else c.tris++;
+            hit = primHitT(q, sph, o, d, tminI, tmaxI) >= 0.0f &&
+                  (INST || S.nprims <= 1 || refLeafBox(q, sph, o, inv, tminI, tmaxI).hit);
+        }
+        fin = fin || hit;
+        if (!fin) {
+            if constexpr (INST) {   // pop; a marker returns to the world ray
+                while ((ng & 0xffu) == 0u && sp > 0) {
+                    sp--;
+                    ng = my[sp * kWave];
+                    if (ng == kInstMarker) { o = wo2; d = wd; inv = winv; oct = woct; ng = 0u; }
+                }
+                if ((ng & 0xffu) == 0u) fin = true;
+            } else if ((ng & 0xffu) == 0u) {
+                if (sp == 0) fin = true;
+                else { sp--; ng = my[sp * kWave]; }
+            }
+        }
+        if (!fin) {
+            const uint32_t bit = (uint32_t)__builtin_ctz(ng & 0xffu);
+            const uint32_t child = (ng >> 8) + (bit ^ oct);
+            ng &= ~(1u << bit);
+            if (ng & 0xffu) {
+                if (sp >= STACK) { atomicOr(S.err, 2u); fin = true; }
+                else { my[sp * kWave] = ng; sp++; }
+            }
+            if (!fin) {
+                c.visits++;
+                const uint32_t off = mul80(child);
+                const uint4 n0 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off, 0, 0));
+                const uint4 n1 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 16u, 0, 0));
+                const uint4 n2 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 32u, 0, 0));
+                const uint4 n3 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 48u, 0, 0));
+                const uint4 n4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 64u, 0, 0));
+                if (INST && n0.w == kInstFlag) {   // an instance: into its object space and bottom-level tree
+                    if (n0.x == 0u) {
+                        const float4 r0 = __builtin_bit_cast(float4, n2), r1 = __builtin_bit_cast(float4, n3),
+                                     r2 = __builtin_bit_cast(float4, n4);
+                        o = xformPoint(r0, r1, r2, wo2);
+                        d = xformDir(r0, r1, r2, wd);
+                        inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));
+                        oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
+                    }
+                    if (sp >= STACK) { atomicOr(S.err, 2u); fin = true; }
+                    else {
+                        my[sp * kWave] = kInstMarker;
+                        sp++;
+                        ng = (n1.x << 8) | (1u << oct);
+                        tg = 0u;
+                    }
+                } else {
+                    const uint32_t h = INST ? wideHitsInst(n0, n1, n2, n3, n4, o, inv, oct, tminI, tmaxI)
+                                            : wideHits<PT_WIDE_MIX != 0>(n0, n1, n2, n3, n4, o, inv, oct, tminI, tmaxI);
+                    ng = (n1.x << 8) | (h >> 24);
+                    tgBase = n1.y;
+                    tg = h & 0xffffffu;
+                }
+            }
+        }
+        if (fin) {
+            occ[ray] = hit ? 1 : 0;
+            ray = -1;
+        }
+    }
+    waveReduceAdd(counters + 0, c.rays);
+    waveReduceAdd(counters + 1, c.visits);
+    waveReduceAdd(counters + 2, c.tris);
+    waveReduceAdd(counters + 3, c.spheres);
+}
+
 // initRandom (main.cu:262-269): curand_init(seed, pixel, 0).  The subsequence skip is the
 // GF(2) product of jump matrices J_k = M^(2^(67+k)) for the set bits of the pixel index.
 // Loops are wave-uniform (k, j); column loads are uniform, hence scalar.
@@ -3713,6 +3939,37 @@ int dispatchTrace(int stack, bool wide, const DevScene& S, const pt_ray* r, int6
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
+// pt_trace_occluded: the queued kernel of either tree (dispatchTrace's grid).
+int dispatchOccluded(int stack, bool wide, const DevScene& S, const pt_ray* r, int64_t n, float tmin, float tmax,
+                     const float* rt, uint8_t* occ, unsigned long long* cnt, hipStream_t st) {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        cus = 256;
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + kWave - 1) / kWave, (int64_t)cus * 32);
+    if (wide) {
+        switch (stack) {
+            case 8: S.winst ? occludedKernelWideQ<8, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt)
+                            : occludedKernelWideQ<8, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
+            case 16: S.winst ? occludedKernelWideQ<16, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt)
+                             : occludedKernelWideQ<16, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
+            case 24: S.winst ? occludedKernelWideQ<24, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt)
+                             : occludedKernelWideQ<24, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
+            default: return fail(PT_ERR_STATE, "unsupported wide BVH depth");
+        }
+    } else {
+        switch (stack) {
+            case 16: occludedKernelQ<16><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
+            case 24: occludedKernelQ<24><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
+            case 32: occludedKernelQ<32><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
+            case 48: occludedKernelQ<48><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
+            case 64: occludedKernelQ<64><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
+            case 80: occludedKernelQ<80><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
+            default: return fail(PT_ERR_STATE, "unsupported BVH depth");
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
 
 // (Re)initialise every stream of the film to curand_init(seed, pixel, 0), asynchronously.
 int filmInit(pt_film* f, hipStream_t st) {
@@ -4212,6 +4469,72 @@ int pt_trace_closest_device(pt_scene* s, const pt_ray* rays, int64_t n, float tm
                             pt_hit* hits, void* stream, pt_stats* stats) {
     if (!s || n < 0 || (n > 0 && (!rays || !hits))) return fail(PT_ERR_INVALID, "pt_trace_closest_device: bad argument");
     return traceDevice(s, rays, n, tmin, tmax, kernel, hits, static_cast<hipStream_t>(stream), stats);
+}
+
+}  // extern "C"
+
+namespace {
+// Occlusion flags of n rays: dr / drt / docc are device arrays, traced on `st`; the host waits for
+// the end, as traceDevice.  PT_KERNEL_DEFAULT is the wide tree here: the answer has no order to honour.
+int occludedDevice(pt_scene* s, const pt_ray* dr, int64_t n, float tmin, float tmax, const float* drt, int kernel,
+                   uint8_t* docc, hipStream_t st, pt_stats* stats) {
+    if (kernel != PT_KERNEL_DEFAULT && kernel != PT_KERNEL_SIMPLE && kernel != PT_KERNEL_WAVEFRONT &&
+        kernel != PT_KERNEL_WIDE)
+        return fail(PT_ERR_INVALID, "pt_trace_occluded: unknown kernel");
+    if (!s->built) return fail(PT_ERR_STATE, "BVH not built");
+    int rc = setDevice(s->device);
+    if (rc) return rc;
+    const bool wide = kernel == PT_KERNEL_DEFAULT || kernel == PT_KERNEL_WIDE;
+    if (s->instanced && !wide)
+        return fail(PT_ERR_INVALID, "pt_trace_occluded: instanced scenes trace with the wide kernel");
+    if (wide && (rc = ensureWide(s))) return rc;
+    const int stack = wide ? wideStackFor(s->wideDepth) : (s->nobj > 1 ? stackFor(s->depth) : 16);
+    StreamGuard guard(st);
+    HIP_TRY(hipMemsetAsync(s->counters.p, 0, kNumCounters * sizeof(unsigned long long), st));
+    HIP_TRY(hipEventCreate(&guard.e0));
+    HIP_TRY(hipEventCreate(&guard.e1));
+    HIP_TRY(hipEventRecord(guard.e0, st));
+    if (n > 0 && (rc = dispatchOccluded(stack, wide, devScene(s), dr, n, tmin, tmax, drt, docc,
+                                        s->counters.as<unsigned long long>(), st)))
+        return rc;
+    HIP_TRY(hipEventRecord(guard.e1, st));
+    HIP_TRY(hipEventSynchronize(guard.e1));
+    guard.ok = true;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, guard.e0, guard.e1));
+    unsigned long long c[kNumCounters] = {0};
+    HIP_TRY(hipMemcpy(c, s->counters.p, sizeof(c), hipMemcpyDeviceToHost));
+    c[4] = 0;
+    fillStats(stats, c, ms, wide);
+    if (c[7]) return fail(PT_ERR_STATE, "traversal guard tripped (corrupt BVH), flags " + std::to_string(c[7]));
+    return PT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pt_trace_occluded(pt_scene* s, const pt_ray* rays, int64_t n, float tmin, float tmax, const float* ray_tmax,
+                      int kernel, uint8_t* occluded, pt_stats* stats) {
+    if (!s || n < 0 || (n > 0 && (!rays || !occluded))) return fail(PT_ERR_INVALID, "pt_trace_occluded: bad argument");
+    int rc = setDevice(s->device);
+    if (rc) return rc;
+    DevBuf dr, dt, dq;
+    if ((rc = devAlloc(dr, n * sizeof(pt_ray))) || (rc = devAlloc(dq, n))) return rc;
+    if (ray_tmax && (rc = devAlloc(dt, n * sizeof(float)))) return rc;
+    if (n > 0) HIP_TRY(hipMemcpy(dr.p, rays, n * sizeof(pt_ray), hipMemcpyHostToDevice));
+    if (n > 0 && ray_tmax) HIP_TRY(hipMemcpy(dt.p, ray_tmax, n * sizeof(float), hipMemcpyHostToDevice));
+    if ((rc = occludedDevice(s, dr.as<pt_ray>(), n, tmin, tmax, n > 0 && ray_tmax ? dt.as<float>() : nullptr, kernel,
+                             dq.as<uint8_t>(), 0, stats)))
+        return rc;
+    if (n > 0) HIP_TRY(hipMemcpy(occluded, dq.p, n, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_trace_occluded_device(pt_scene* s, const pt_ray* rays, int64_t n, float tmin, float tmax, const float* ray_tmax,
+                             int kernel, uint8_t* occluded, void* stream, pt_stats* stats) {
+    if (!s || n < 0 || (n > 0 && (!rays || !occluded)))
+        return fail(PT_ERR_INVALID, "pt_trace_occluded_device: bad argument");
+    return occludedDevice(s, rays, n, tmin, tmax, ray_tmax, kernel, occluded, static_cast<hipStream_t>(stream), stats);
 }
 
 int pt_film_create(int device, int width, int height, int sh, int nparts, int part, uint64_t seed, pt_film** out) {

@@ -5,10 +5,10 @@
 #include <string>
 
 namespace pt {
-inline std::string& lastError() {
-    static thread_local std::string msg;
-    return msg;
-}
+// One definition (pt_host.cpp) for every translation unit: an inline function's local static is
+// mangled differently by the host compiler and by hipcc, which gave the HIP units a string of
+// their own that pt_last_error() never read.
+std::string& lastError();
 inline int fail(int code, const std::string& msg) {
     lastError() = msg;
     return code;

@@ -449,6 +449,11 @@ void mortonKeys(const pt_object* objs, int64_t n, bool includeOrigin, uint64_t* 
     for (int64_t i = 0; i < n; i++) keys[i] = ((uint64_t)m[(size_t)i].first << 32) | m[(size_t)i].second;
 }
 
+std::string& lastError() {   // (pt_error.hpp)
+    static thread_local std::string msg;
+    return msg;
+}
+
 }  // namespace pt
 
 // ================================================================== C ABI (host part)

@@ -90,7 +90,7 @@ EXPORTS = [
     "pt_film_clear", "pt_film_accumulated", "pt_write_png_rgba8", "pt_scene_build_time",
     "pt_scene_update_objects", "pt_trace_closest_ex", "pt_scene_wide_info", "pt_trace_closest_device",
     "pt_scene_build_bvh_ex", "pt_film_stats", "pt_preset_instanced", "pt_instanced_desc_free",
-    "pt_scene_create_instanced",
+    "pt_scene_create_instanced", "pt_trace_occluded", "pt_trace_occluded_device",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -137,6 +137,9 @@ _sig = {
     "pt_trace_closest_ex": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_float, C.c_int, _P, C.POINTER(Stats)]),
     "pt_trace_closest_device": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_float, C.c_int, _P, _P,
                                           C.POINTER(Stats)]),
+    "pt_trace_occluded": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_float, _P, C.c_int, _P, C.POINTER(Stats)]),
+    "pt_trace_occluded_device": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_float, _P, C.c_int, _P, _P,
+                                           C.POINTER(Stats)]),
     "pt_film_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64,
                                  C.POINTER(C.c_void_p)]),
     "pt_film_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
@@ -381,6 +384,32 @@ class Scene:
         st = Stats()
         _check(lib.pt_trace_closest_device(self.h, rays_ptr or None, n, tmin, tmax, kernel, hits_ptr or None,
                                            stream, C.byref(st)), "pt_trace_closest_device")
+        return st
+
+    def occluded(self, rays: np.ndarray, tmin: float = 0.001, tmax: float = float("inf"), ray_tmax=None,
+                 kernel: int = KERNEL_DEFAULT):
+        """Any-hit flags (pt_trace_occluded): uint8, 1 exactly where trace() of the same ray and interval
+        reports a hit.  ray_tmax: one tmax per ray (then `tmax` is ignored).  KERNEL_DEFAULT is the
+        8-wide tree here."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        occ = np.zeros(len(rays), np.uint8)
+        rt = None
+        if ray_tmax is not None:
+            rt = np.ascontiguousarray(ray_tmax, np.float32)
+            assert rt.shape == (len(rays),)
+        st = Stats()
+        _check(lib.pt_trace_occluded(self.h, _ptr(rays) if len(rays) else None, len(rays), tmin, tmax,
+                                     _ptr(rt) if rt is not None and len(rt) else None, kernel,
+                                     _ptr(occ) if len(occ) else None, C.byref(st)), "pt_trace_occluded")
+        return occ, st
+
+    def occluded_device(self, rays_ptr: int, n: int, out_ptr: int, tmin: float = 0.001, tmax: float = float("inf"),
+                        ray_tmax_ptr=None, kernel: int = KERNEL_DEFAULT, stream=None):
+        """pt_trace_occluded_device: rays_ptr / out_ptr / ray_tmax_ptr are device pointers to n RAY_DTYPE
+        records, n bytes and n floats (or None), e.g. torch tensors' data_ptr(); returns the stats."""
+        st = Stats()
+        _check(lib.pt_trace_occluded_device(self.h, rays_ptr or None, n, tmin, tmax, ray_tmax_ptr or None, kernel,
+                                            out_ptr or None, stream, C.byref(st)), "pt_trace_occluded_device")
         return st
 
     def close(self) -> None:
