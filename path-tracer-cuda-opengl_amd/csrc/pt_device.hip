@@ -2165,6 +2165,259 @@ __global__ __launch_bounds__(256) void tileKeyKernel(const unsigned* __restrict_
     ids[i] = (uint32_t)i;
 }
 
+// ------------------------------------------------------------------------ ray queries
+// Six query kernels: closest hit on the binary tree (traceKernel, queued: traceKernelQ) and on the
+// wide tree (traceKernelWide, traceKernelWideQ), any hit on either tree (occludedKernelQ,
+// occludedKernelWideQ).  Each is a composition of the pieces below, which exist once: the hit
+// records, the binary tree's query start and node visit (binStart, binVisit), the wide walk's
+// query start, closest-hit primitive group and node step (wideStart, wideGroupClosest, wideStep).
+
+__device__ __forceinline__ void flushCounters(unsigned long long* counters, const Counters& c) {
+    waveReduceAdd(counters + 0, c.rays);
+    waveReduceAdd(counters + 1, c.visits);
+    waveReduceAdd(counters + 2, c.tris);
+    waveReduceAdd(counters + 3, c.spheres);
+}
+
+__device__ __forceinline__ pt_hit missRecord() {
+    pt_hit h = {};
+    h.obj = -1;
+    h.mat = -1;
+    return h;
+}
+__device__ __forceinline__ pt_hit hitRecord(const HitRec& x, float t) {
+    pt_hit h = missRecord();
+    h.hit = 1;
+    h.obj = x.obj;
+    h.mat = x.mat;
+    h.front_face = x.front ? 1 : 0;
+    h.t = t;
+    h.p[0] = x.p.x; h.p[1] = x.p.y; h.p[2] = x.p.z;
+    h.n[0] = x.n.x; h.n[1] = x.n.y; h.n[2] = x.n.z;
+    return h;
+}
+// The binary tree's record: leaf slot k (< 0: a miss) at distance t.
+__device__ __forceinline__ pt_hit binHit(const DevScene& S, int k, float t, float3 o, float3 d) {
+    return k >= 0 ? hitRecord(makeHit(S, k, t, o, d), t) : missRecord();
+}
+
+// One primitive test of a fixed interval (any hit), counted as primTest counts it.
+__device__ __forceinline__ bool primTestAny(const DevScene& S, uint32_t ref, float3 o, float3 d, float tmin, float tmax,
+                                            Counters& c) {
+    const bool sph = (ref & kSphereBit) != 0;
+    if (sph) c.spheres++;
+    else c.tris++;
+    return primHitT(loadPrim(S, ref & kPrimMask), sph, o, d, tmin, tmax) >= 0.0f;
+}
+
+// A lane's walk of the binary tree in the reference's order (trace<STACK>), one node visit at a
+// time.  `hi` is the interval's upper bound: closest hit shrinks it to the nearest hit so far and
+// keeps that leaf in `best`; ANY keeps it fixed and stops at the first accepted primitive, with
+// best = 0 for "hit" (-1: none).
+struct BinWalk {
+    float3 o, d, inv;
+    int node, sp, guard;
+};
+template <bool ANY>
+__device__ __forceinline__ bool binLeaf(const DevScene& S, uint32_t ref, const BinWalk& w, float tmin, float& hi,
+                                        int& best, Counters& c) {   // true: the walk ends here
+    if constexpr (ANY) {
+        const bool hit = primTestAny(S, ref, w.o, w.d, tmin, hi, c);
+        best = hit ? 0 : -1;
+        return hit;
+    } else {
+        primTest(S, ref, w.o, w.d, tmin, hi, best, c);
+        return false;
+    }
+}
+// The query's start; true: it is already answered (no tree to walk).
+template <bool ANY>
+__device__ __forceinline__ bool binStart(const DevScene& S, pt_ray r, float tmin, float tmax, BinWalk& w, float& hi,
+                                         int& best, Counters& c) {
+    w.o = f3(r.o[0], r.o[1], r.o[2]);
+    w.d = f3(r.d[0], r.d[1], r.d[2]);
+    hi = tmax;
+    best = -1;
+    c.rays++;
+    if (S.nprims <= 1) {
+        if (S.nprims == 1)   // root is a leaf: tested without a box test (:92-98)
+            binLeaf<ANY>(S, kLeafBit | (__float_as_uint(S.prims[2].w) ? kSphereBit : 0u), w, tmin, hi, best, c);
+        return true;
+    }
+    w.inv = f3(rcpRN(w.d.x), rcpRN(w.d.y), rcpRN(w.d.z));
+    w.node = 0;
+    w.sp = 0;
+    w.guard = 0;
+    return false;
+}
+// One node visit: both children's slab tests, a leaf child tested at once, an internal child
+// pushed (left, then right), then the pop.  true: the walk ended.
+template <int STACK, bool ANY>
+__device__ __forceinline__ bool binVisit(const DevScene& S, uint32_t* my, float tmin, BinWalk& w, float& hi, int& best,
+                                         Counters& c) {
+    if (++w.guard > S.nprims) { atomicOr(S.err, 1u); return true; }   // (a corrupt tree, trace<STACK>)
+    c.visits++;
+    const float4* np = S.nodes + 4 * (size_t)w.node;
+    const float4 a = np[0], b = np[1], q = np[2], rr = np[3];
+    const uint32_t lref = __float_as_uint(rr.x), rref = __float_as_uint(rr.y);   // (read here: one 16-B load)
+    const auto child = [&](uint32_t ref) {   // a child whose box passed
+        if (ref & kLeafBit) return binLeaf<ANY>(S, ref, w, tmin, hi, best, c);
+        if (w.sp < STACK) { my[w.sp * kWave] = ref; w.sp++; return false; }
+        atomicOr(S.err, 2u);
+        return true;
+    };
+    if (slabLeft(a, b, w.o, w.inv, tmin, hi).hit && child(lref)) return true;
+    if (slabRight(b, q, w.o, w.inv, tmin, hi).hit && child(rref)) return true;
+    if (w.sp == 0) return true;
+    w.sp--;
+    w.node = (int)my[w.sp * kWave];
+    return false;
+}
+
+// A lane's walk of the wide tree: the same traversal as renderKernelWF's WIDE steps, one lane per
+// ray.  INST: an instanced scene's two-level tree (renderKernelWF<.., INST>).
+struct WideWalk {
+    float3 wo2, wd, winv;   // the world ray (instanced, far origin: moved to its entry into the world)
+    float3 o, d, inv;       // the ray walked (inside an instance: in its object space)
+    uint32_t woct, oct, inst;  // inst: the instance entered (read by the closest-hit kernels only)
+    uint32_t ng, tgBase, tg;   // the node's remaining children; the primitive group to test
+    float shift, tminI;        // (tmin, tmax of the moved ray: t - shift)
+    int sp;
+    uint32_t visits;   // the query's node visits: read by traceKernelWideQ under PT_TRACE_DIAG_VISITS only, else dead
+};
+// The query's start: the walk's state and `hi`, the interval's (shifted) upper bound.  true: a far
+// origin, or a direction the MIX planes cannot take; the walk is empty and the caller answers the
+// query in the reference's order.
+template <bool INST>
+__device__ __forceinline__ bool wideStart(const DevScene& S, pt_ray r, float tmin, float tmax, WideWalk& w, float& hi,
+                                          Counters& c) {
+    const float3 wo = f3(r.o[0], r.o[1], r.o[2]);
+    w.wd = f3(r.d[0], r.d[1], r.d[2]);
+    w.winv = f3(rcpRN(w.wd.x), rcpRN(w.wd.y), rcpRN(w.wd.z));
+    w.woct = (w.winv.x < 0.0f ? 1u : 0u) | (w.winv.y < 0.0f ? 2u : 0u) | (w.winv.z < 0.0f ? 4u : 0u);
+    w.o = wo; w.d = w.wd; w.inv = w.winv;
+    w.oct = w.woct;
+    w.inst = 0u;
+    const bool far = !INST && (wideFar(S, w.o) || (PT_WIDE_MIX && mixUnsafe(w.winv, S.mixLim)));
+    // instanced: a far origin moves to the ray's entry into the world (instEntry); distances
+    // are then measured from there and shifted back at the end
+    w.wo2 = wo;
+    w.shift = (INST && instFar(S, wo)) ? instEntry(S.cx, S.cy, S.cz, S.ext, w.wo2, w.wd, w.winv) : 0.0f;
+    if (INST) w.o = w.wo2;
+    w.tminI = tmin - w.shift;
+    hi = tmax - w.shift;
+    w.sp = 0;
+    w.ng = S.nprims > 0 && !far ? (1u << w.oct) : 0u;
+    w.tgBase = 0u;
+    w.tg = 0u;
+    w.visits = 0u;
+    c.rays++;
+    return far;
+}
+// One step after the lane's primitive group: pop (a marker returns to the world ray), the nearest
+// remaining child, the rest pushed, the node's load, then the instance's entry or the node test
+// over [tminI, hi].  true: the walk ended (or overflowed its stack, flagged).
+template <int STACK, bool INST>
+__device__ __forceinline__ bool wideStep(const DevScene& S, __amdgpu_buffer_rsrc_t nodeRsrc, uint32_t* my, float hi,
+                                         WideWalk& w, Counters& c) {
+    if constexpr (INST) {
+        while ((w.ng & 0xffu) == 0u && w.sp > 0) {
+            w.sp--;
+            w.ng = my[w.sp * kWave];
+            if (w.ng == kInstMarker) { w.o = w.wo2; w.d = w.wd; w.inv = w.winv; w.oct = w.woct; w.ng = 0u; }
+        }
+        if ((w.ng & 0xffu) == 0u) return true;
+    } else if ((w.ng & 0xffu) == 0u) {
+        if (w.sp == 0) return true;
+        w.sp--;
+        w.ng = my[w.sp * kWave];
+    }
+    const uint32_t bit = (uint32_t)__builtin_ctz(w.ng & 0xffu);
+    const uint32_t child = (w.ng >> 8) + (bit ^ w.oct);
+    w.ng &= ~(1u << bit);
+    if (w.ng & 0xffu) {
+        if (w.sp >= STACK) { atomicOr(S.err, 2u); return true; }
+        my[w.sp * kWave] = w.ng;
+        w.sp++;
+    }
+    c.visits++;
+    w.visits++;
+    const uint32_t off = mul80(child);
+    const uint4 n0 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off, 0, 0));
+    const uint4 n1 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 16u, 0, 0));
+    const uint4 n2 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 32u, 0, 0));
+    const uint4 n3 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 48u, 0, 0));
+    const uint4 n4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 64u, 0, 0));
+    if (INST && n0.w == kInstFlag) {   // an instance: into its object space and bottom-level tree
+        if (n0.x == 0u) {
+            const float4 r0 = __builtin_bit_cast(float4, n2), r1 = __builtin_bit_cast(float4, n3),
+                         r2 = __builtin_bit_cast(float4, n4);
+            w.o = xformPoint(r0, r1, r2, w.wo2);
+            w.d = xformDir(r0, r1, r2, w.wd);
+            w.inv = f3(rcpRN(w.d.x), rcpRN(w.d.y), rcpRN(w.d.z));
+            w.oct = (w.inv.x < 0.0f ? 1u : 0u) | (w.inv.y < 0.0f ? 2u : 0u) | (w.inv.z < 0.0f ? 4u : 0u);
+        }
+        if (w.sp >= STACK) { atomicOr(S.err, 2u); return true; }
+        my[w.sp * kWave] = kInstMarker;
+        w.sp++;
+        w.ng = (n1.x << 8) | (1u << w.oct);
+        w.inst = n1.y;
+        w.tg = 0u;
+        return false;
+    }
+    const uint32_t h = INST ? wideHitsInst(n0, n1, n2, n3, n4, w.o, w.inv, w.oct, w.tminI, hi)
+                            : wideHits<PT_WIDE_MIX != 0>(n0, n1, n2, n3, n4, w.o, w.inv, w.oct, w.tminI, hi);
+    w.ng = (n1.x << 8) | (h >> 24);
+    w.tgBase = n1.y;
+    w.tg = h & 0xffffffu;
+    return false;
+}
+
+// The closest-hit walk's result so far (wideTest): `redo` = an order-dependent candidate, the query
+// is answered in the reference's order at the end.
+struct WideBest {
+    float closest, bestLo;
+    int best;
+    bool redo;
+};
+template <bool INST>
+__device__ __forceinline__ void wideStartClosest(const DevScene& S, pt_ray r, float tmin, float tmax, WideWalk& w,
+                                                 WideBest& b, Counters& c) {
+    b.redo = wideStart<INST>(S, r, tmin, tmax, w, b.closest, c);
+    b.best = -1;
+    b.bestLo = -__builtin_inff();
+}
+// The closest-hit tests of the lane's primitive group.
+template <bool INST>
+__device__ __forceinline__ void wideGroupClosest(const DevScene& S, WideWalk& w, WideBest& b, Counters& c) {
+    while (w.tg) {
+        const uint32_t k = w.tgBase + (uint32_t)__builtin_ctz(w.tg);
+        w.tg &= w.tg - 1u;
+        const float4* p = S.wprims + 3 * (size_t)k;
+        const Prim q{p[0], p[1], p[2]};
+        if (__float_as_uint(q.p2.w) != 0u) c.spheres++;
+        else c.tris++;
+        const bool lb = !INST && S.nprims > 1;
+        const uint32_t kh = INST ? w.inst << S.gBits : 0u;
+        if (S.hasSpheres) wideTest<true>(q, w.o, w.d, w.inv, w.tminI, b.closest, b.best, b.bestLo, lb, b.redo, kh);
+        else wideTest<false>(q, w.o, w.d, w.inv, w.tminI, b.closest, b.best, b.bestLo, lb, b.redo, kh);
+    }
+}
+// The finished walk's record, the same as traceKernel's.
+template <bool INST>
+__device__ __forceinline__ pt_hit wideHit(const DevScene& S, const WideWalk& w, WideBest& b, float tmin, float tmax) {
+    if (b.redo) {   // an order-dependent candidate: the query in the reference's order
+        b.closest = tmax;
+        const int k = traceRefStackless(S, w.o, w.d, tmin, b.closest);
+        b.best = k >= 0 ? (int)S.rankOf[k] : -1;
+    }
+    if (b.best < 0) return missRecord();
+    int obj = 0;
+    const HitRec x = INST ? makeHitInst(S, (uint32_t)b.best & kPrimMask, b.closest, w.wo2, w.wd, obj)
+                          : makeHitFrom(S.wshade, b.best & (int)kPrimMask, b.closest, w.o, w.d);
+    return hitRecord(x, INST ? b.closest + w.shift : b.closest);
+}
+
 // pt_trace_closest on the binary LBVH, in the reference order (trace<STACK>).
 template <int STACK>
 __global__ __launch_bounds__(kWave) void traceKernel(DevScene S, const pt_ray* rays, int64_t n, float tmin,
@@ -2182,31 +2435,13 @@ __global__ __launch_bounds__(kWave) void traceKernel(DevScene S, const pt_ray* r
         float closest = tmax;
         c.rays++;
         const int k = trace<STACK>(S, o, d, tmin, closest, stk + lane, c);
-        pt_hit h = {};
-        h.obj = -1;
-        h.mat = -1;
-        if (k >= 0) {
-            HitRec hr = makeHit(S, k, closest, o, d);
-            h.hit = 1;
-            h.obj = hr.obj;
-            h.mat = hr.mat;
-            h.front_face = hr.front ? 1 : 0;
-            h.t = closest;
-            h.p[0] = hr.p.x; h.p[1] = hr.p.y; h.p[2] = hr.p.z;
-            h.n[0] = hr.n.x; h.n[1] = hr.n.y; h.n[2] = hr.n.z;
-        }
-        hits[i] = h;
+        hits[i] = binHit(S, k, closest, o, d);
     }
     }
-    waveReduceAdd(counters + 0, c.rays);
-    waveReduceAdd(counters + 1, c.visits);
-    waveReduceAdd(counters + 2, c.tris);
-    waveReduceAdd(counters + 3, c.spheres);
+    flushCounters(counters, c);
 }
 
-// pt_trace_closest on the wide tree (PT_KERNEL_WIDE): the same traversal as renderKernelWF's
-// WIDE steps, one lane per ray, the same hit records as traceKernel.  INST: an instanced scene's
-// two-level tree (renderKernelWF<.., INST>).
+// pt_trace_closest on the wide tree (PT_KERNEL_WIDE), the same hit records as traceKernel.
 template <int STACK, bool INST>
 __global__ __launch_bounds__(kWave) void traceKernelWide(DevScene S, const pt_ray* rays, int64_t n, float tmin,
                                                          float tmax, pt_hit* hits, unsigned long long* counters) {
@@ -2218,116 +2453,15 @@ __global__ __launch_bounds__(kWave) void traceKernelWide(DevScene S, const pt_ra
     for (int64_t base = (int64_t)blockIdx.x * kWave; base < n; base += (int64_t)gridDim.x * kWave) {   // grid-stride
     const int64_t i = base + lane;
     if (i < n) {
-        const pt_ray r = rays[i];
-        const float3 wo = f3(r.o[0], r.o[1], r.o[2]), wd = f3(r.d[0], r.d[1], r.d[2]);
-        const float3 winv = f3(rcpRN(wd.x), rcpRN(wd.y), rcpRN(wd.z));
-        const uint32_t woct = (winv.x < 0.0f ? 1u : 0u) | (winv.y < 0.0f ? 2u : 0u) | (winv.z < 0.0f ? 4u : 0u);
-        float3 o = wo, d = wd, inv = winv;   // (inside an instance: its object space)
-        uint32_t oct = woct, inst = 0u;
-        // (far origin, or a direction the MIX planes cannot take: the query in the reference's order only)
-        const bool far = !INST && (wideFar(S, o) || (PT_WIDE_MIX && mixUnsafe(winv, S.mixLim)));
-        // instanced: a far origin moves to the ray's entry into the world (instEntry); distances
-        // are then measured from there and shifted back at the end
-        float3 wo2 = wo;
-        const float shift = (INST && instFar(S, wo)) ? instEntry(S.cx, S.cy, S.cz, S.ext, wo2, wd, winv) : 0.0f;
-        if (INST) o = wo2;
-        const float tminI = tmin - shift;   // (tmin, tmax of the moved ray: t - shift)
-        float closest = tmax - shift;
-        int best = -1, sp = 0;
-        bool redo = far;
-        float bestLo = -__builtin_inff();
-        uint32_t ng = S.nprims > 0 && !far ? (1u << oct) : 0u, tgBase = 0u, tg = 0u;
-        c.rays++;
-        for (;;) {
-            while (tg) {
-                const uint32_t k = tgBase + (uint32_t)__builtin_ctz(tg);
-                tg &= tg - 1u;
-                const float4* w = S.wprims + 3 * (size_t)k;
-                const Prim q{w[0], w[1], w[2]};
-                if (__float_as_uint(q.p2.w) != 0u) c.spheres++;
-                else c.tris++;
-                const bool lb = !INST && S.nprims > 1;
-                const uint32_t kh = INST ? inst << S.gBits : 0u;
-                if (S.hasSpheres) wideTest<true>(q, o, d, inv, tminI, closest, best, bestLo, lb, redo, kh);
-                else wideTest<false>(q, o, d, inv, tminI, closest, best, bestLo, lb, redo, kh);
-            }
-            if constexpr (INST) {   // pop; a marker returns to the world ray
-                while ((ng & 0xffu) == 0u && sp > 0) {
-                    sp--;
-                    ng = my[sp * kWave];
-                    if (ng == kInstMarker) { o = wo2; d = wd; inv = winv; oct = woct; ng = 0u; }
-                }
-                if ((ng & 0xffu) == 0u) break;
-            } else if ((ng & 0xffu) == 0u) {
-                if (sp == 0) break;
-                sp--;
-                ng = my[sp * kWave];
-            }
-            const uint32_t bit = (uint32_t)__builtin_ctz(ng & 0xffu);
-            const uint32_t child = (ng >> 8) + (bit ^ oct);
-            ng &= ~(1u << bit);
-            if (ng & 0xffu) {
-                if (sp >= STACK) { atomicOr(S.err, 2u); break; }
-                my[sp * kWave] = ng;
-                sp++;
-            }
-            c.visits++;
-            const uint32_t off = mul80(child);
-            const uint4 n0 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off, 0, 0));
-            const uint4 n1 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 16u, 0, 0));
-            const uint4 n2 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 32u, 0, 0));
-            const uint4 n3 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 48u, 0, 0));
-            const uint4 n4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 64u, 0, 0));
-            if (INST && n0.w == kInstFlag) {   // an instance: into its object space and bottom-level tree
-                if (n0.x == 0u) {
-                    const float4 r0 = __builtin_bit_cast(float4, n2), r1 = __builtin_bit_cast(float4, n3),
-                                 r2 = __builtin_bit_cast(float4, n4);
-                    o = xformPoint(r0, r1, r2, wo2);
-                    d = xformDir(r0, r1, r2, wd);
-                    inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));
-                    oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
-                }
-                if (sp >= STACK) { atomicOr(S.err, 2u); break; }
-                my[sp * kWave] = kInstMarker;
-                sp++;
-                ng = (n1.x << 8) | (1u << oct);
-                inst = n1.y;
-                tg = 0u;
-                continue;
-            }
-            const uint32_t h = INST ? wideHitsInst(n0, n1, n2, n3, n4, o, inv, oct, tminI, closest)
-                                    : wideHits<PT_WIDE_MIX != 0>(n0, n1, n2, n3, n4, o, inv, oct, tminI, closest);
-            ng = (n1.x << 8) | (h >> 24);
-            tgBase = n1.y;
-            tg = h & 0xffffffu;
-        }
-        if (redo) {   // an order-dependent candidate: the query in the reference's order
-            closest = tmax;
-            const int k = traceRefStackless(S, o, d, tmin, closest);
-            best = k >= 0 ? (int)S.rankOf[k] : -1;
-        }
-        pt_hit hr = {};
-        hr.obj = -1;
-        hr.mat = -1;
-        if (best >= 0) {
-            int obj = 0;
-            HitRec x = INST ? makeHitInst(S, (uint32_t)best & kPrimMask, closest, wo2, wd, obj)
-                            : makeHitFrom(S.wshade, best & (int)kPrimMask, closest, o, d);
-            hr.hit = 1;
-            hr.obj = x.obj;
-            hr.mat = x.mat;
-            hr.front_face = x.front ? 1 : 0;
-            hr.t = INST ? closest + shift : closest;
-            hr.p[0] = x.p.x; hr.p[1] = x.p.y; hr.p[2] = x.p.z;
-            hr.n[0] = x.n.x; hr.n[1] = x.n.y; hr.n[2] = x.n.z;
-        }
-        hits[i] = hr;
+        WideWalk w;
+        WideBest b;
+        wideStartClosest<INST>(S, rays[i], tmin, tmax, w, b, c);
+        do wideGroupClosest<INST>(S, w, b, c);
+        while (!wideStep<STACK, INST>(S, nodeRsrc, my, b.closest, w, c));
+        hits[i] = wideHit<INST>(S, w, b, tmin, tmax);
     }
     }
-    waveReduceAdd(counters + 0, c.rays);
-    waveReduceAdd(counters + 1, c.visits);
-    waveReduceAdd(counters + 2, c.tris);
-    waveReduceAdd(counters + 3, c.spheres);
+    flushCounters(counters, c);
 }
 
 // Queued closest-hit kernels (the default for pt_trace_closest; PT_TRACE_STRIDE=1 selects the
@@ -2337,9 +2471,9 @@ __global__ __launch_bounds__(kWave) void traceKernelWide(DevScene S, const pt_ra
 // slowest ray is done.  The lanes that ask are ranked by a ballot and an mbcnt prefix count and
 // served, in lane order, from the wave's pool of kTraceGrab consecutive rays (one returning
 // atomic per pool on a queue word of the scene's counters).  Each loop iteration runs one
-// traversal step per lane -- the reference order's node visit with its leaf tests (traceKernel),
-// or the wide tree's primitive group + next node (traceKernelWide) -- with exactly those
-// kernels' arithmetic, so every hit record and work counter is the same.
+// traversal step per lane -- the reference order's node visit with its leaf tests (binVisit),
+// or the wide tree's primitive group + next node (wideGroupClosest, wideStep) -- the very code
+// of the grid-stride kernels, so every hit record and work counter is the same.
 #ifndef PT_TRACE_GRAB
 #define PT_TRACE_GRAB 256   // rays per queue grab (a wave's pool)
 #endif
@@ -2388,7 +2522,7 @@ constexpr int kTraceQueue = 24;   // counters[24]: the ray queue (zeroed with th
     } while (0)
 
 // traceKernel (the reference's order, render_manager.h:86-135) with the ray queue: one node visit
-// (both children's slab tests and leaf tests, trace<STACK>) per lane and iteration.
+// per lane and iteration.
 template <int STACK>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_WAVES))) void traceKernelQ(DevScene S, const pt_ray* rays, int64_t n, float tmin,
                                                       float tmax, pt_hit* hits, unsigned long long* counters) {
@@ -2399,80 +2533,21 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_
     int64_t ray = -1, poolBase = 0;
     uint32_t poolLeft = 0u;
     bool more = true;
-    float3 o = f3(0.0f, 0.0f, 0.0f), d = o, inv = o;
+    BinWalk w = {};
     float closest = 0.0f;
-    int best = -1, node = 0, sp = 0, guard = 0;
+    int best = -1;
     for (;;) {
         bool took = false;
         PT_TRACE_REFILL(took);
         if (__ballot(ray >= 0) == 0) break;
         if (ray < 0) continue;
-        bool fin = false;
-        if (took) {   // the query's start (trace<STACK>)
-            const pt_ray r = rays[ray];
-            o = f3(r.o[0], r.o[1], r.o[2]);
-            d = f3(r.d[0], r.d[1], r.d[2]);
-            closest = tmax;
-            best = -1;
-            c.rays++;
-            if (S.nprims <= 1) {
-                if (S.nprims == 1) {   // root is a leaf: tested without a box test (:92-98)
-                    const uint32_t ref = kLeafBit | (__float_as_uint(S.prims[2].w) ? kSphereBit : 0u);
-                    primTest(S, ref, o, d, tmin, closest, best, c);
-                }
-                fin = true;
-            } else {
-                inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));
-                node = 0;
-                sp = 0;
-                guard = 0;
-            }
-        }
-        if (!fin) {   // one node visit of trace<STACK>
-            if (++guard > S.nprims) { atomicOr(S.err, 1u); fin = true; }
-            else {
-                c.visits++;
-                const float4* np = S.nodes + 4 * (size_t)node;
-                const float4 a = np[0], b = np[1], q = np[2], rr = np[3];
-                const uint32_t lref = __float_as_uint(rr.x), rref = __float_as_uint(rr.y);
-                if (slabLeft(a, b, o, inv, tmin, closest).hit) {
-                    if (lref & kLeafBit) primTest(S, lref, o, d, tmin, closest, best, c);
-                    else if (sp < STACK) { my[sp * kWave] = lref; sp++; }
-                    else { atomicOr(S.err, 2u); fin = true; }
-                }
-                if (!fin && slabRight(b, q, o, inv, tmin, closest).hit) {
-                    if (rref & kLeafBit) primTest(S, rref, o, d, tmin, closest, best, c);
-                    else if (sp < STACK) { my[sp * kWave] = rref; sp++; }
-                    else { atomicOr(S.err, 2u); fin = true; }
-                }
-                if (!fin) {
-                    if (sp == 0) fin = true;
-                    else { sp--; node = (int)my[sp * kWave]; }
-                }
-            }
-        }
-        if (fin) {   // the hit record (traceKernel)
-            pt_hit h = {};
-            h.obj = -1;
-            h.mat = -1;
-            if (best >= 0) {
-                HitRec hr = makeHit(S, best, closest, o, d);
-                h.hit = 1;
-                h.obj = hr.obj;
-                h.mat = hr.mat;
-                h.front_face = hr.front ? 1 : 0;
-                h.t = closest;
-                h.p[0] = hr.p.x; h.p[1] = hr.p.y; h.p[2] = hr.p.z;
-                h.n[0] = hr.n.x; h.n[1] = hr.n.y; h.n[2] = hr.n.z;
-            }
-            hits[ray] = h;
+        if ((took && binStart<false>(S, rays[ray], tmin, tmax, w, closest, best, c)) ||
+            binVisit<STACK, false>(S, my, tmin, w, closest, best, c)) {
+            hits[ray] = binHit(S, best, closest, w.o, w.d);
             ray = -1;
         }
     }
-    waveReduceAdd(counters + 0, c.rays);
-    waveReduceAdd(counters + 1, c.visits);
-    waveReduceAdd(counters + 2, c.tris);
-    waveReduceAdd(counters + 3, c.spheres);
+    flushCounters(counters, c);
 }
 
 // traceKernelWide with the ray queue: per lane and iteration, the current primitive group's tests
@@ -2488,140 +2563,24 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_
     int64_t ray = -1, poolBase = 0;
     uint32_t poolLeft = 0u;
     bool more = true;
-    float3 wo2 = f3(0.0f, 0.0f, 0.0f), wd = wo2, winv = wo2, o = wo2, d = wo2, inv = wo2;
-    uint32_t woct = 0u, oct = 0u, inst = 0u, ng = 0u, tgBase = 0u, tg = 0u;
-    float shift = 0.0f, tminI = 0.0f, closest = 0.0f, bestLo = 0.0f;
-    int best = -1, sp = 0;
-    bool redo = false;
-    uint32_t qVisits = 0u;   // (PT_TRACE_DIAG_VISITS)
+    WideWalk w = {};
+    WideBest b = {0.0f, 0.0f, -1, false};
     for (;;) {
         bool took = false;
         PT_TRACE_REFILL(took);
         if (__ballot(ray >= 0) == 0) break;
         if (ray < 0) continue;
-        if (took) {   // the query's start (traceKernelWide)
-            const pt_ray r = rays[ray];
-            const float3 wo = f3(r.o[0], r.o[1], r.o[2]);
-            wd = f3(r.d[0], r.d[1], r.d[2]);
-            winv = f3(rcpRN(wd.x), rcpRN(wd.y), rcpRN(wd.z));
-            woct = (winv.x < 0.0f ? 1u : 0u) | (winv.y < 0.0f ? 2u : 0u) | (winv.z < 0.0f ? 4u : 0u);
-            o = wo; d = wd; inv = winv;
-            oct = woct;
-            inst = 0u;
-            const bool far = !INST && (wideFar(S, o) || (PT_WIDE_MIX && mixUnsafe(winv, S.mixLim)));
-            wo2 = wo;
-            shift = (INST && instFar(S, wo)) ? instEntry(S.cx, S.cy, S.cz, S.ext, wo2, wd, winv) : 0.0f;
-            if (INST) o = wo2;
-            tminI = tmin - shift;
-            closest = tmax - shift;
-            best = -1;
-            sp = 0;
-            redo = far;
-            bestLo = -__builtin_inff();
-            ng = S.nprims > 0 && !far ? (1u << oct) : 0u;
-            tgBase = 0u;
-            tg = 0u;
-            c.rays++;
-            qVisits = 0u;
-        }
-        while (tg) {
-            const uint32_t k = tgBase + (uint32_t)__builtin_ctz(tg);
-            tg &= tg - 1u;
-            const float4* w = S.wprims + 3 * (size_t)k;
-            const Prim q{w[0], w[1], w[2]};
-            if (__float_as_uint(q.p2.w) != 0u) c.spheres++;
-            else c.tris++;
-            const bool lb = !INST && S.nprims > 1;
-            const uint32_t kh = INST ? inst << S.gBits : 0u;
-            if (S.hasSpheres) wideTest<true>(q, o, d, inv, tminI, closest, best, bestLo, lb, redo, kh);
-            else wideTest<false>(q, o, d, inv, tminI, closest, best, bestLo, lb, redo, kh);
-        }
-        bool fin = false;
-        if constexpr (INST) {   // pop; a marker returns to the world ray
-            while ((ng & 0xffu) == 0u && sp > 0) {
-                sp--;
-                ng = my[sp * kWave];
-                if (ng == kInstMarker) { o = wo2; d = wd; inv = winv; oct = woct; ng = 0u; }
-            }
-            if ((ng & 0xffu) == 0u) fin = true;
-        } else if ((ng & 0xffu) == 0u) {
-            if (sp == 0) fin = true;
-            else { sp--; ng = my[sp * kWave]; }
-        }
-        if (!fin) {
-            const uint32_t bit = (uint32_t)__builtin_ctz(ng & 0xffu);
-            const uint32_t child = (ng >> 8) + (bit ^ oct);
-            ng &= ~(1u << bit);
-            if (ng & 0xffu) {
-                if (sp >= STACK) { atomicOr(S.err, 2u); fin = true; }
-                else { my[sp * kWave] = ng; sp++; }
-            }
-            if (!fin) {
-                c.visits++;
-                qVisits++;
-                const uint32_t off = mul80(child);
-                const uint4 n0 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off, 0, 0));
-                const uint4 n1 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 16u, 0, 0));
-                const uint4 n2 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 32u, 0, 0));
-                const uint4 n3 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 48u, 0, 0));
-                const uint4 n4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 64u, 0, 0));
-                if (INST && n0.w == kInstFlag) {   // an instance: into its object space and bottom-level tree
-                    if (n0.x == 0u) {
-                        const float4 r0 = __builtin_bit_cast(float4, n2), r1 = __builtin_bit_cast(float4, n3),
-                                     r2 = __builtin_bit_cast(float4, n4);
-                        o = xformPoint(r0, r1, r2, wo2);
-                        d = xformDir(r0, r1, r2, wd);
-                        inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));
-                        oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
-                    }
-                    if (sp >= STACK) { atomicOr(S.err, 2u); fin = true; }
-                    else {
-                        my[sp * kWave] = kInstMarker;
-                        sp++;
-                        ng = (n1.x << 8) | (1u << oct);
-                        inst = n1.y;
-                        tg = 0u;
-                    }
-                } else {
-                    const uint32_t h = INST ? wideHitsInst(n0, n1, n2, n3, n4, o, inv, oct, tminI, closest)
-                                            : wideHits<PT_WIDE_MIX != 0>(n0, n1, n2, n3, n4, o, inv, oct, tminI, closest);
-                    ng = (n1.x << 8) | (h >> 24);
-                    tgBase = n1.y;
-                    tg = h & 0xffffffu;
-                }
-            }
-        }
-        if (fin) {   // the reference-order redo and the hit record (traceKernelWide)
-            if (PT_TRACE_DIAG_REDO && redo) c.spheres++;
-            if (redo) {
-                closest = tmax;
-                const int k = traceRefStackless(S, o, d, tmin, closest);
-                best = k >= 0 ? (int)S.rankOf[k] : -1;
-            }
-            pt_hit hr = {};
-            hr.obj = -1;
-            hr.mat = -1;
-            if (best >= 0) {
-                int obj = 0;
-                HitRec x = INST ? makeHitInst(S, (uint32_t)best & kPrimMask, closest, wo2, wd, obj)
-                                : makeHitFrom(S.wshade, best & (int)kPrimMask, closest, o, d);
-                hr.hit = 1;
-                hr.obj = x.obj;
-                hr.mat = x.mat;
-                hr.front_face = x.front ? 1 : 0;
-                hr.t = INST ? closest + shift : closest;
-                hr.p[0] = x.p.x; hr.p[1] = x.p.y; hr.p[2] = x.p.z;
-                hr.n[0] = x.n.x; hr.n[1] = x.n.y; hr.n[2] = x.n.z;
-            }
-            if (PT_TRACE_DIAG_VISITS) hr.mat = (int)qVisits;
-            hits[ray] = hr;
+        if (took) wideStartClosest<INST>(S, rays[ray], tmin, tmax, w, b, c);
+        wideGroupClosest<INST>(S, w, b, c);
+        if (wideStep<STACK, INST>(S, nodeRsrc, my, b.closest, w, c)) {
+            if (PT_TRACE_DIAG_REDO && b.redo) c.spheres++;
+            pt_hit h = wideHit<INST>(S, w, b, tmin, tmax);
+            if (PT_TRACE_DIAG_VISITS) h.mat = (int)w.visits;
+            hits[ray] = h;
             ray = -1;
         }
     }
-    waveReduceAdd(counters + 0, c.rays);
-    waveReduceAdd(counters + 1, c.visits);
-    waveReduceAdd(counters + 2, c.tris);
-    waveReduceAdd(counters + 3, c.spheres);
+    flushCounters(counters, c);
 }
 
 // ------------------------------------------------------------------------ occlusion (any hit)
@@ -2635,18 +2594,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_
 // the closest-hit kernels' walk up to their first accepted hit, hence never more work.
 // rayTmax (optional): per-ray tmax, replacing the scalar.
 
-// One primitive test of the fixed interval, counted as primTest counts it.
-__device__ __forceinline__ bool primTestAny(const DevScene& S, uint32_t ref, float3 o, float3 d, float tmin, float tmax,
-                                            Counters& c) {
-    const bool sph = (ref & kSphereBit) != 0;
-    if (sph) c.spheres++;
-    else c.tris++;
-    return primHitT(loadPrim(S, ref & kPrimMask), sph, o, d, tmin, tmax) >= 0.0f;
-}
-
 // pt_trace_occluded on the binary LBVH (PT_KERNEL_SIMPLE / PT_KERNEL_WAVEFRONT): traceKernelQ's walk
-// (the reference's visiting order, trace<STACK>, with the ray queue) with the interval fixed at the
-// ray's tmax; a lane stops at the first accepted primitive and takes the next ray.
+// (binStart / binVisit with ANY) with the interval fixed at the ray's tmax; a lane stops at the
+// first accepted primitive and takes the next ray.
 template <int STACK>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_WAVES))) void occludedKernelQ(
     DevScene S, const pt_ray* rays, int64_t n, float tmin, float tmax, const float* __restrict__ rayTmax, uint8_t* occ,
@@ -2658,73 +2608,30 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_
     int64_t ray = -1, poolBase = 0;
     uint32_t poolLeft = 0u;
     bool more = true;
-    float3 o = f3(0.0f, 0.0f, 0.0f), d = o, inv = o;
+    BinWalk w = {};
     float tmaxR = 0.0f;
-    int node = 0, sp = 0, guard = 0;
+    int best = -1;
     for (;;) {
         bool took = false;
         PT_TRACE_REFILL(took);
         if (__ballot(ray >= 0) == 0) break;
         if (ray < 0) continue;
-        bool fin = false, hit = false;
-        if (took) {   // the query's start (trace<STACK>)
-            const pt_ray r = rays[ray];
-            o = f3(r.o[0], r.o[1], r.o[2]);
-            d = f3(r.d[0], r.d[1], r.d[2]);
-            tmaxR = rayTmax ? rayTmax[ray] : tmax;
-            c.rays++;
-            if (S.nprims <= 1) {
-                if (S.nprims == 1)   // root is a leaf: tested without a box test (:92-98)
-                    hit = primTestAny(S, kLeafBit | (__float_as_uint(S.prims[2].w) ? kSphereBit : 0u), o, d, tmin, tmaxR, c);
-                fin = true;
-            } else {
-                inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));
-                node = 0;
-                sp = 0;
-                guard = 0;
-            }
-        }
-        if (!fin) {   // one node visit of trace<STACK>
-            if (++guard > S.nprims) { atomicOr(S.err, 1u); fin = true; }
-            else {
-                c.visits++;
-                const float4* np = S.nodes + 4 * (size_t)node;
-                const float4 a = np[0], b = np[1], q = np[2], rr = np[3];
-                const uint32_t lref = __float_as_uint(rr.x), rref = __float_as_uint(rr.y);
-                if (slabLeft(a, b, o, inv, tmin, tmaxR).hit) {
-                    if (lref & kLeafBit) hit = primTestAny(S, lref, o, d, tmin, tmaxR, c);
-                    else if (sp < STACK) { my[sp * kWave] = lref; sp++; }
-                    else { atomicOr(S.err, 2u); fin = true; }
-                }
-                if (!fin && !hit && slabRight(b, q, o, inv, tmin, tmaxR).hit) {
-                    if (rref & kLeafBit) hit = primTestAny(S, rref, o, d, tmin, tmaxR, c);
-                    else if (sp < STACK) { my[sp * kWave] = rref; sp++; }
-                    else { atomicOr(S.err, 2u); fin = true; }
-                }
-                fin = fin || hit;
-                if (!fin) {
-                    if (sp == 0) fin = true;
-                    else { sp--; node = (int)my[sp * kWave]; }
-                }
-            }
-        }
-        if (fin) {
-            occ[ray] = hit ? 1 : 0;
+        if ((took && binStart<true>(S, rays[ray], tmin, rayTmax ? rayTmax[ray] : tmax, w, tmaxR, best, c)) ||
+            binVisit<STACK, true>(S, my, tmin, w, tmaxR, best, c)) {
+            occ[ray] = best >= 0 ? 1 : 0;
             ray = -1;
         }
     }
-    waveReduceAdd(counters + 0, c.rays);
-    waveReduceAdd(counters + 1, c.visits);
-    waveReduceAdd(counters + 2, c.tris);
-    waveReduceAdd(counters + 3, c.spheres);
+    flushCounters(counters, c);
 }
 
-// pt_trace_occluded on the wide tree: traceKernelWideQ's walk (ray queue, node loads, node tests,
-// nearest-first child order) with the interval fixed at the ray's tmax, one lane per ray; a lane
-// stops at the first primitive that passes the contract's test and takes the next ray.  A far
-// origin or a direction the MIX planes cannot take (wideFar, mixUnsafe) is answered by the
-// reference-order query's flag, as in the closest-hit kernel (no work counted there either).
-// INST: the two-level walk; no leaf boxes, so the test is (a) alone in the instance's space.
+// pt_trace_occluded on the wide tree: traceKernelWideQ's walk (ray queue, wideStart, wideStep:
+// node loads, node tests, nearest-first child order) with the interval fixed at the ray's tmax,
+// one lane per ray; a lane stops at the first primitive that passes the contract's test and takes
+// the next ray.  A far origin or a direction the MIX planes cannot take (wideFar, mixUnsafe) is
+// answered by the reference-order query's flag, as in the closest-hit kernel (no work counted
+// there either).  INST: the two-level walk; no leaf boxes, so the test is (a) alone in the
+// instance's space.
 template <int STACK, bool INST>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_WAVES))) void occludedKernelWideQ(
     DevScene S, const pt_ray* rays, int64_t n, float tmin, float tmax, const float* __restrict__ rayTmax, uint8_t* occ,
@@ -2737,117 +2644,39 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_
     int64_t ray = -1, poolBase = 0;
     uint32_t poolLeft = 0u;
     bool more = true;
-    float3 wo2 = f3(0.0f, 0.0f, 0.0f), wd = wo2, winv = wo2, o = wo2, d = wo2, inv = wo2;
-    uint32_t woct = 0u, oct = 0u, ng = 0u, tgBase = 0u, tg = 0u;
-    float tminI = 0.0f, tmaxI = 0.0f;
-    int sp = 0;
+    WideWalk w = {};
+    float tmaxI = 0.0f;
     for (;;) {
         bool took = false;
         PT_TRACE_REFILL(took);
         if (__ballot(ray >= 0) == 0) break;
         if (ray < 0) continue;
         bool hit = false, fin = false;
-        if (took) {   // the query's start (traceKernelWideQ)
-            const pt_ray r = rays[ray];
-            const float3 wo = f3(r.o[0], r.o[1], r.o[2]);
+        if (took) {
             const float tmaxR = rayTmax ? rayTmax[ray] : tmax;
-            wd = f3(r.d[0], r.d[1], r.d[2]);
-            winv = f3(rcpRN(wd.x), rcpRN(wd.y), rcpRN(wd.z));
-            woct = (winv.x < 0.0f ? 1u : 0u) | (winv.y < 0.0f ? 2u : 0u) | (winv.z < 0.0f ? 4u : 0u);
-            o = wo; d = wd; inv = winv;
-            oct = woct;
-            const bool far = !INST && (wideFar(S, o) || (PT_WIDE_MIX && mixUnsafe(winv, S.mixLim)));
-            wo2 = wo;
-            const float shift = (INST && instFar(S, wo)) ? instEntry(S.cx, S.cy, S.cz, S.ext, wo2, wd, winv) : 0.0f;
-            if (INST) o = wo2;
-            tminI = tmin - shift;
-            tmaxI = tmaxR - shift;
-            sp = 0;
-            ng = S.nprims > 0 && !far ? (1u << oct) : 0u;
-            tgBase = 0u;
-            tg = 0u;
-            c.rays++;
-            if (far) {   // the query in the reference's order: its flag
+            if (wideStart<INST>(S, rays[ray], tmin, tmaxR, w, tmaxI, c)) {   // the query in the reference's order: its flag
                 float closest = tmaxR;
-                hit = traceRefStackless(S, o, d, tmin, closest) >= 0;
+                hit = traceRefStackless(S, w.o, w.d, tmin, closest) >= 0;
                 fin = true;
             }
         }
-        while (tg && !hit) {
-            const uint32_t k = tgBase + (uint32_t)__builtin_ctz(tg);
-            tg &= tg - 1u;
-            const float4* w = S.wprims + 3 * (size_t)k;
-            const Prim q{w[0], w[1], w[2]};
+        while (w.tg && !hit) {
+            const uint32_t k = w.tgBase + (uint32_t)__builtin_ctz(w.tg);
+            w.tg &= w.tg - 1u;
+            const float4* p = S.wprims + 3 * (size_t)k;
+            const Prim q{p[0], p[1], p[2]};
             const bool sph = __float_as_uint(q.p2.w) != 0u;
             if (sph) c.spheres++;
             else c.tris++;
-            hit = primHitT(q, sph, o, d, tminI, tmaxI) >= 0.0f &&
-                  (INST || S.nprims <= 1 || refLeafBox(q, sph, o, inv, tminI, tmaxI).hit);
+            hit = primHitT(q, sph, w.o, w.d, w.tminI, tmaxI) >= 0.0f &&
+                  (INST || S.nprims <= 1 || refLeafBox(q, sph, w.o, w.inv, w.tminI, tmaxI).hit);
         }
-        fin = fin || hit;
-        if (!fin) {
-            if constexpr (INST) {   // pop; a marker returns to the world ray
-                while ((ng & 0xffu) == 0u && sp > 0) {
-                    sp--;
-                    ng = my[sp * kWave];
-                    if (ng == kInstMarker) { o = wo2; d = wd; inv = winv; oct = woct; ng = 0u; }
-                }
-                if ((ng & 0xffu) == 0u) fin = true;
-            } else if ((ng & 0xffu) == 0u) {
-                if (sp == 0) fin = true;
-                else { sp--; ng = my[sp * kWave]; }
-            }
-        }
-        if (!fin) {
-            const uint32_t bit = (uint32_t)__builtin_ctz(ng & 0xffu);
-            const uint32_t child = (ng >> 8) + (bit ^ oct);
-            ng &= ~(1u << bit);
-            if (ng & 0xffu) {
-                if (sp >= STACK) { atomicOr(S.err, 2u); fin = true; }
-                else { my[sp * kWave] = ng; sp++; }
-            }
-            if (!fin) {
-                c.visits++;
-                const uint32_t off = mul80(child);
-                const uint4 n0 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off, 0, 0));
-                const uint4 n1 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 16u, 0, 0));
-                const uint4 n2 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 32u, 0, 0));
-                const uint4 n3 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 48u, 0, 0));
-                const uint4 n4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 64u, 0, 0));
-                if (INST && n0.w == kInstFlag) {   // an instance: into its object space and bottom-level tree
-                    if (n0.x == 0u) {
-                        const float4 r0 = __builtin_bit_cast(float4, n2), r1 = __builtin_bit_cast(float4, n3),
-                                     r2 = __builtin_bit_cast(float4, n4);
-                        o = xformPoint(r0, r1, r2, wo2);
-                        d = xformDir(r0, r1, r2, wd);
-                        inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));
-                        oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
-                    }
-                    if (sp >= STACK) { atomicOr(S.err, 2u); fin = true; }
-                    else {
-                        my[sp * kWave] = kInstMarker;
-                        sp++;
-                        ng = (n1.x << 8) | (1u << oct);
-                        tg = 0u;
-                    }
-                } else {
-                    const uint32_t h = INST ? wideHitsInst(n0, n1, n2, n3, n4, o, inv, oct, tminI, tmaxI)
-                                            : wideHits<PT_WIDE_MIX != 0>(n0, n1, n2, n3, n4, o, inv, oct, tminI, tmaxI);
-                    ng = (n1.x << 8) | (h >> 24);
-                    tgBase = n1.y;
-                    tg = h & 0xffffffu;
-                }
-            }
-        }
-        if (fin) {
+        if (fin || hit || wideStep<STACK, INST>(S, nodeRsrc, my, tmaxI, w, c)) {
             occ[ray] = hit ? 1 : 0;
             ray = -1;
         }
     }
-    waveReduceAdd(counters + 0, c.rays);
-    waveReduceAdd(counters + 1, c.visits);
-    waveReduceAdd(counters + 2, c.tris);
-    waveReduceAdd(counters + 3, c.spheres);
+    flushCounters(counters, c);
 }
 
 // initRandom (main.cu:262-269): curand_init(seed, pixel, 0).  The subsequence skip is the
@@ -3820,153 +3649,82 @@ int wavesPerCU(int& n) {
                                                          kWave, 0));
     return PT_OK;
 }
+// A run-time stack size as a compile-time constant: f(std::integral_constant<int, N>) for the N
+// of `Ns` that equals `stack`; false when there is none (an unsupported depth).  The lists are
+// wideStackFor's and stackFor's, so exactly those kernels are instantiated.
+template <int... Ns, class F>
+bool withStack(int stack, F f) {
+    return ((stack == Ns && (f(std::integral_constant<int, Ns>{}), true)) || ...);
+}
+template <class F>
+bool withWideStack(int stack, F f) { return withStack<8, 16, 24>(stack, f); }
+template <class F>
+bool withBinStack(int stack, F f) { return withStack<16, 24, 32, 48, 64, 80>(stack, f); }
+
 // Waves per CU of the render kernel a launch runs: its occupancy (sample mode launches exactly the
 // waves that fit; compat launches do not ask).  The compat wide kernels live in pt_compat.hip's
 // translation unit.
 int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample) {
-    if (kernel == PT_KERNEL_WIDE && inst) {
-        switch (stack) {
-            case 8: return sample ? wavesPerCU<8, true, true>(n) : wavesPerCU<8, true, true, false>(n);
-            case 16: return sample ? wavesPerCU<16, true, true>(n) : wavesPerCU<16, true, true, false>(n);
-            case 24: return sample ? wavesPerCU<24, true, true>(n) : wavesPerCU<24, true, true, false>(n);
-            default: return fail(PT_ERR_STATE, "unsupported instanced BVH depth");
-        }
-    }
-    if (kernel == PT_KERNEL_WIDE) {
-        if (!sample) return pt::compatWideWavesPerCU(stack, n) ? fail(PT_ERR_STATE, "unsupported wide BVH depth") : PT_OK;
-        switch (stack) {
-            case 8: return wavesPerCU<8, true>(n);
-            case 16: return wavesPerCU<16, true>(n);
-            case 24: return wavesPerCU<24, true>(n);
-            default: return fail(PT_ERR_STATE, "unsupported wide BVH depth");
-        }
-    }
-    switch (stack) {
-        case 16: return sample ? wavesPerCU<16, false>(n) : wavesPerCU<16, false, false, false>(n);
-        case 24: return sample ? wavesPerCU<24, false>(n) : wavesPerCU<24, false, false, false>(n);
-        case 32: return sample ? wavesPerCU<32, false>(n) : wavesPerCU<32, false, false, false>(n);
-        case 48: return sample ? wavesPerCU<48, false>(n) : wavesPerCU<48, false, false, false>(n);
-        case 64: return sample ? wavesPerCU<64, false>(n) : wavesPerCU<64, false, false, false>(n);
-        case 80: return sample ? wavesPerCU<80, false>(n) : wavesPerCU<80, false, false, false>(n);
-        default: return fail(PT_ERR_STATE, "unsupported BVH depth");
-    }
+    const bool wide = kernel == PT_KERNEL_WIDE;
+    if (wide && !inst && !sample)
+        return pt::compatWideWavesPerCU(stack, n) ? fail(PT_ERR_STATE, "unsupported wide BVH depth") : PT_OK;
+    int rc = PT_OK;
+    const bool ok = wide ? withWideStack(stack, [&](auto N) {
+        constexpr int K = decltype(N)::value;
+        rc = !inst ? wavesPerCU<K, true>(n) : sample ? wavesPerCU<K, true, true>(n) : wavesPerCU<K, true, true, false>(n);
+    }) : withBinStack(stack, [&](auto N) {
+        constexpr int K = decltype(N)::value;
+        rc = sample ? wavesPerCU<K, false>(n) : wavesPerCU<K, false, false, false>(n);
+    });
+    if (!ok) return fail(PT_ERR_STATE, !wide ? "unsupported BVH depth" : inst ? "unsupported instanced BVH depth" : "unsupported wide BVH depth");
+    return rc;
 }
 int dispatchRender(int stack, const RenderParams& P, hipStream_t st) {
-    if (P.kernel == PT_KERNEL_WIDE) {
-        switch (stack) {
-            case 8: launchRenderWide<8>(P, st); break;
-            case 16: launchRenderWide<16>(P, st); break;
-            case 24: launchRenderWide<24>(P, st); break;
-            default: return fail(PT_ERR_STATE, "unsupported wide BVH depth");
-        }
-        HIP_TRY(hipGetLastError());
-        return PT_OK;
-    }
-    switch (stack) {
-        case 16: launchRender<16>(P, st); break;
-        case 24: launchRender<24>(P, st); break;
-        case 32: launchRender<32>(P, st); break;
-        case 48: launchRender<48>(P, st); break;
-        case 64: launchRender<64>(P, st); break;
-        case 80: launchRender<80>(P, st); break;
-        default: return fail(PT_ERR_STATE, "unsupported BVH depth");
-    }
+    const bool wide = P.kernel == PT_KERNEL_WIDE;
+    const bool ok = wide ? withWideStack(stack, [&](auto N) { launchRenderWide<decltype(N)::value>(P, st); })
+                         : withBinStack(stack, [&](auto N) { launchRender<decltype(N)::value>(P, st); });
+    if (!ok) return fail(PT_ERR_STATE, wide ? "unsupported wide BVH depth" : "unsupported BVH depth");
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
+
+// The ray queries' grid: at most 32 one-wave blocks per CU (the grid-stride kernels stride over
+// the batch, the queued ones take rays from its queue).
+unsigned queryBlocks(int64_t n) {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        cus = 256;
+    return (unsigned)std::min<int64_t>((n + kWave - 1) / kWave, (int64_t)cus * 32);
+}
+// pt_trace_closest: the queued kernel of either tree; PT_TRACE_STRIDE=1: the grid-stride one (A/B).
 int dispatchTrace(int stack, bool wide, const DevScene& S, const pt_ray* r, int64_t n, float tmin, float tmax,
                   pt_hit* h, unsigned long long* cnt, hipStream_t st) {
-    // a grid of at most 32 one-wave blocks per CU, striding over the batch
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + kWave - 1) / kWave, (int64_t)cus * 32);
-    const char* strideEnv = std::getenv("PT_TRACE_STRIDE");   // 1: the grid-stride kernels (A/B)
-    if (!(strideEnv && std::atoi(strideEnv) != 0)) {   // default: the queued kernels
-        if (wide) {
-            switch (stack) {
-                case 8: S.winst ? traceKernelWideQ<8, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt)
-                                : traceKernelWideQ<8, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-                case 16: S.winst ? traceKernelWideQ<16, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt)
-                                 : traceKernelWideQ<16, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-                case 24: S.winst ? traceKernelWideQ<24, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt)
-                                 : traceKernelWideQ<24, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-                default: return fail(PT_ERR_STATE, "unsupported wide BVH depth");
-            }
-        } else {
-            switch (stack) {
-                case 16: traceKernelQ<16><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-                case 24: traceKernelQ<24><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-                case 32: traceKernelQ<32><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-                case 48: traceKernelQ<48><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-                case 64: traceKernelQ<64><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-                case 80: traceKernelQ<80><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-                default: return fail(PT_ERR_STATE, "unsupported BVH depth");
-            }
-        }
-        HIP_TRY(hipGetLastError());
-        return PT_OK;
-    }
-    if (wide && S.winst) {
-        switch (stack) {
-            case 8: traceKernelWide<8, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-            case 16: traceKernelWide<16, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-            case 24: traceKernelWide<24, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-            default: return fail(PT_ERR_STATE, "unsupported instanced BVH depth");
-        }
-        HIP_TRY(hipGetLastError());
-        return PT_OK;
-    }
-    if (wide) {
-        switch (stack) {
-            case 8: traceKernelWide<8, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-            case 16: traceKernelWide<16, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-            case 24: traceKernelWide<24, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-            default: return fail(PT_ERR_STATE, "unsupported wide BVH depth");
-        }
-        HIP_TRY(hipGetLastError());
-        return PT_OK;
-    }
-    switch (stack) {
-        case 16: traceKernel<16><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-        case 24: traceKernel<24><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-        case 32: traceKernel<32><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-        case 48: traceKernel<48><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-        case 64: traceKernel<64><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-        case 80: traceKernel<80><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); break;
-        default: return fail(PT_ERR_STATE, "unsupported BVH depth");
-    }
+    const char* strideEnv = std::getenv("PT_TRACE_STRIDE");
+    const bool stride = strideEnv && std::atoi(strideEnv) != 0;
+    const auto launch = [&](auto* kernel) { kernel<<<queryBlocks(n), kWave, 0, st>>>(S, r, n, tmin, tmax, h, cnt); };
+    const bool ok = wide ? withWideStack(stack, [&](auto N) {
+        constexpr int K = decltype(N)::value;
+        if (S.winst) launch(stride ? traceKernelWide<K, true> : traceKernelWideQ<K, true>);
+        else launch(stride ? traceKernelWide<K, false> : traceKernelWideQ<K, false>);
+    }) : withBinStack(stack, [&](auto N) {
+        constexpr int K = decltype(N)::value;
+        launch(stride ? traceKernel<K> : traceKernelQ<K>);
+    });
+    if (!ok)   // (the texts of the former tables: "instanced" only ever appeared on the grid-stride path)
+        return fail(PT_ERR_STATE, !wide ? "unsupported BVH depth"
+                                        : stride && S.winst ? "unsupported instanced BVH depth" : "unsupported wide BVH depth");
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
-// pt_trace_occluded: the queued kernel of either tree (dispatchTrace's grid).
+// pt_trace_occluded: the queued kernel of either tree.
 int dispatchOccluded(int stack, bool wide, const DevScene& S, const pt_ray* r, int64_t n, float tmin, float tmax,
                      const float* rt, uint8_t* occ, unsigned long long* cnt, hipStream_t st) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + kWave - 1) / kWave, (int64_t)cus * 32);
-    if (wide) {
-        switch (stack) {
-            case 8: S.winst ? occludedKernelWideQ<8, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt)
-                            : occludedKernelWideQ<8, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
-            case 16: S.winst ? occludedKernelWideQ<16, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt)
-                             : occludedKernelWideQ<16, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
-            case 24: S.winst ? occludedKernelWideQ<24, true><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt)
-                             : occludedKernelWideQ<24, false><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
-            default: return fail(PT_ERR_STATE, "unsupported wide BVH depth");
-        }
-    } else {
-        switch (stack) {
-            case 16: occludedKernelQ<16><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
-            case 24: occludedKernelQ<24><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
-            case 32: occludedKernelQ<32><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
-            case 48: occludedKernelQ<48><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
-            case 64: occludedKernelQ<64><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
-            case 80: occludedKernelQ<80><<<blocks, kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); break;
-            default: return fail(PT_ERR_STATE, "unsupported BVH depth");
-        }
-    }
+    const auto launch = [&](auto* kernel) { kernel<<<queryBlocks(n), kWave, 0, st>>>(S, r, n, tmin, tmax, rt, occ, cnt); };
+    const bool ok = wide ? withWideStack(stack, [&](auto N) {
+        constexpr int K = decltype(N)::value;
+        launch(S.winst ? occludedKernelWideQ<K, true> : occludedKernelWideQ<K, false>);
+    }) : withBinStack(stack, [&](auto N) { launch(occludedKernelQ<decltype(N)::value>); });
+    if (!ok) return fail(PT_ERR_STATE, wide ? "unsupported wide BVH depth" : "unsupported BVH depth");
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
@@ -4414,19 +4172,22 @@ int pt_trace_closest(pt_scene* s, const pt_ray* rays, int64_t n, float tmin, flo
 }  // extern "C"
 
 namespace {
-// Closest hits of n rays: rays / hits are device arrays (dr, dh), traced on `st`; the host waits
-// for the end (counters and the guard word are read back).
-int traceDevice(pt_scene* s, const pt_ray* dr, int64_t n, float tmin, float tmax, int kernel, pt_hit* dh,
-                hipStream_t st, pt_stats* stats) {
+// A batch of n ray queries on device arrays, traced on `st`; the host waits for the end (counters
+// and the guard word are read back).  `who` prefixes the messages; defaultWide: PT_KERNEL_DEFAULT
+// is the wide tree (closest hit: for instanced scenes only; occlusion: always, the answer has no
+// order to honour); launch(stack, wide, scene, counters) is dispatchTrace or dispatchOccluded.
+template <class Launch>
+int queryDevice(pt_scene* s, const char* who, int kernel, bool defaultWide, int64_t n, hipStream_t st, pt_stats* stats,
+                Launch launch) {
     if (kernel != PT_KERNEL_DEFAULT && kernel != PT_KERNEL_SIMPLE && kernel != PT_KERNEL_WAVEFRONT &&
         kernel != PT_KERNEL_WIDE)
-        return fail(PT_ERR_INVALID, "pt_trace_closest: unknown kernel");
+        return fail(PT_ERR_INVALID, std::string(who) + ": unknown kernel");
     if (!s->built) return fail(PT_ERR_STATE, "BVH not built");
     int rc = setDevice(s->device);
     if (rc) return rc;
-    const bool wide = kernel == PT_KERNEL_WIDE || s->instanced;
-    if (s->instanced && kernel != PT_KERNEL_DEFAULT && kernel != PT_KERNEL_WIDE)
-        return fail(PT_ERR_INVALID, "pt_trace_closest: instanced scenes trace with the wide kernel");
+    const bool wide = kernel == PT_KERNEL_WIDE || (kernel == PT_KERNEL_DEFAULT && defaultWide);
+    if (s->instanced && !wide)
+        return fail(PT_ERR_INVALID, std::string(who) + ": instanced scenes trace with the wide kernel");
     if (wide && (rc = ensureWide(s))) return rc;
     const int stack = wide ? wideStackFor(s->wideDepth) : (s->nobj > 1 ? stackFor(s->depth) : 16);
     StreamGuard guard(st);
@@ -4434,8 +4195,7 @@ int traceDevice(pt_scene* s, const pt_ray* dr, int64_t n, float tmin, float tmax
     HIP_TRY(hipEventCreate(&guard.e0));
     HIP_TRY(hipEventCreate(&guard.e1));
     HIP_TRY(hipEventRecord(guard.e0, st));
-    if (n > 0 && (rc = dispatchTrace(stack, wide, devScene(s), dr, n, tmin, tmax, dh, s->counters.as<unsigned long long>(), st)))
-        return rc;
+    if (n > 0 && (rc = launch(stack, wide, devScene(s), s->counters.as<unsigned long long>()))) return rc;
     HIP_TRY(hipEventRecord(guard.e1, st));
     HIP_TRY(hipEventSynchronize(guard.e1));
     guard.ok = true;
@@ -4447,6 +4207,21 @@ int traceDevice(pt_scene* s, const pt_ray* dr, int64_t n, float tmin, float tmax
     fillStats(stats, c, ms, wide);
     if (c[7]) return fail(PT_ERR_STATE, "traversal guard tripped (corrupt BVH), flags " + std::to_string(c[7]));
     return PT_OK;
+}
+// Closest hits / occlusion flags of n rays: dr, dh / drt, docc are device arrays.
+int traceDevice(pt_scene* s, const pt_ray* dr, int64_t n, float tmin, float tmax, int kernel, pt_hit* dh,
+                hipStream_t st, pt_stats* stats) {
+    return queryDevice(s, "pt_trace_closest", kernel, s->instanced, n, st, stats,
+                       [&](int stack, bool wide, const DevScene& S, unsigned long long* cnt) {
+                           return dispatchTrace(stack, wide, S, dr, n, tmin, tmax, dh, cnt, st);
+                       });
+}
+int occludedDevice(pt_scene* s, const pt_ray* dr, int64_t n, float tmin, float tmax, const float* drt, int kernel,
+                   uint8_t* docc, hipStream_t st, pt_stats* stats) {
+    return queryDevice(s, "pt_trace_occluded", kernel, true, n, st, stats,
+                       [&](int stack, bool wide, const DevScene& S, unsigned long long* cnt) {
+                           return dispatchOccluded(stack, wide, S, dr, n, tmin, tmax, drt, docc, cnt, st);
+                       });
 }
 }  // namespace
 
@@ -4470,48 +4245,6 @@ int pt_trace_closest_device(pt_scene* s, const pt_ray* rays, int64_t n, float tm
     if (!s || n < 0 || (n > 0 && (!rays || !hits))) return fail(PT_ERR_INVALID, "pt_trace_closest_device: bad argument");
     return traceDevice(s, rays, n, tmin, tmax, kernel, hits, static_cast<hipStream_t>(stream), stats);
 }
-
-}  // extern "C"
-
-namespace {
-// Occlusion flags of n rays: dr / drt / docc are device arrays, traced on `st`; the host waits for
-// the end, as traceDevice.  PT_KERNEL_DEFAULT is the wide tree here: the answer has no order to honour.
-int occludedDevice(pt_scene* s, const pt_ray* dr, int64_t n, float tmin, float tmax, const float* drt, int kernel,
-                   uint8_t* docc, hipStream_t st, pt_stats* stats) {
-    if (kernel != PT_KERNEL_DEFAULT && kernel != PT_KERNEL_SIMPLE && kernel != PT_KERNEL_WAVEFRONT &&
-        kernel != PT_KERNEL_WIDE)
-        return fail(PT_ERR_INVALID, "pt_trace_occluded: unknown kernel");
-    if (!s->built) return fail(PT_ERR_STATE, "BVH not built");
-    int rc = setDevice(s->device);
-    if (rc) return rc;
-    const bool wide = kernel == PT_KERNEL_DEFAULT || kernel == PT_KERNEL_WIDE;
-    if (s->instanced && !wide)
-        return fail(PT_ERR_INVALID, "pt_trace_occluded: instanced scenes trace with the wide kernel");
-    if (wide && (rc = ensureWide(s))) return rc;
-    const int stack = wide ? wideStackFor(s->wideDepth) : (s->nobj > 1 ? stackFor(s->depth) : 16);
-    StreamGuard guard(st);
-    HIP_TRY(hipMemsetAsync(s->counters.p, 0, kNumCounters * sizeof(unsigned long long), st));
-    HIP_TRY(hipEventCreate(&guard.e0));
-    HIP_TRY(hipEventCreate(&guard.e1));
-    HIP_TRY(hipEventRecord(guard.e0, st));
-    if (n > 0 && (rc = dispatchOccluded(stack, wide, devScene(s), dr, n, tmin, tmax, drt, docc,
-                                        s->counters.as<unsigned long long>(), st)))
-        return rc;
-    HIP_TRY(hipEventRecord(guard.e1, st));
-    HIP_TRY(hipEventSynchronize(guard.e1));
-    guard.ok = true;
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, guard.e0, guard.e1));
-    unsigned long long c[kNumCounters] = {0};
-    HIP_TRY(hipMemcpy(c, s->counters.p, sizeof(c), hipMemcpyDeviceToHost));
-    c[4] = 0;
-    fillStats(stats, c, ms, wide);
-    if (c[7]) return fail(PT_ERR_STATE, "traversal guard tripped (corrupt BVH), flags " + std::to_string(c[7]));
-    return PT_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int pt_trace_occluded(pt_scene* s, const pt_ray* rays, int64_t n, float tmin, float tmax, const float* ray_tmax,
                       int kernel, uint8_t* occluded, pt_stats* stats) {
