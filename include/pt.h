@@ -154,7 +154,8 @@ int pt_scene_create(int device, const pt_object* objs, int64_t n_objects,
  * dynamic scenes rebuilt every frame).  Without it PT_KERNEL_WIDE builds the tree at first use on
  * the host (binned SAH, slower to build; PT_WIDE_BUILD=device selects the device build there
  * too; after pt_scene_update_objects the device build is the default).  Either tree gives the
- * same images. */
+ * same images.  On an instanced scene the flag means "lay the scene out for instance updates"
+ * (pt_scene_update_instances). */
 #define PT_BVH_WIDE_DEVICE 4
 int pt_scene_build_bvh(pt_scene* scene, int flags);
 /* pt_scene_build_bvh with its device work enqueued on `stream` (a hipStream_t, NULL = the null
@@ -181,13 +182,42 @@ int pt_scene_create_instanced(int device, const pt_object* objs, int64_t n_objec
  * device buffer of the previous build (no allocation, no device-wide synchronisation).  The
  * reference has no counterpart: it builds once (main.cu:122-128 / bvh.h:132-145). */
 int pt_scene_update_objects(pt_scene* scene, const pt_object* objs, int64_t first, int64_t n);
+/* Moving instances (rigid animation of an instanced scene): overwrite the transforms of instances
+ * [first, first + n) from a host array and mark the hierarchy stale -- rendering, tracing and
+ * occlusion queries fail with PT_ERR_STATE until pt_scene_build_bvh / _ex runs again.  PT_ERR_INVALID
+ * (and the scene left exactly as it was) for a scene that is not instanced, a range outside
+ * [0, n_instances], a NULL array with n > 0, an instances[i].mesh different from the instance's
+ * current mesh (the flattened object numbering and the hit key depend on it: create a new scene), a
+ * non-finite matrix entry, or a singular matrix (|det| <= 1e-30 or not finite, the build's rule; the
+ * message names the instance).  n == 0 changes nothing.
+ * The builds of a scene whose instances were updated (or that was once built with
+ * PT_BVH_WIDE_DEVICE, which for an instanced scene means "lay the scene out for updates"): the
+ * first is the full host build, with the top level's region of the node array reserved at its upper
+ * bound and the mesh trees quantised for twice the world's current reach into their object spaces;
+ * every later one keeps the mesh trees, primitive and shading records and redoes only what depends
+ * on the matrices -- the instances' exact world boxes and their entries' boxes on the device, on
+ * the build's stream (every vertex of every instance in fp64), then the top-level 8-wide tree over the
+ * entries (the device wide builder's SAH and collapse stages, one entry per leaf, written into the
+ * reserved region) and its instance records; the world-to-object rows (64 B per instance) and the
+ * scene scalars are computed on the host by the full build's own code, the scalars from the
+ * instances' boxes read back.  No device allocation, no host tree build (pt_scene_wide_info source
+ * 4; pt_scene_build_time: the device time of that work, HIP events).
+ * When a mesh's new reach exceeds the reach its tree was built for, that build is the full one
+ * again (source 3).  A rebuilt scene returns bit for bit the hits and frames of a fresh scene of
+ * the same matrices -- as far as the primitive tests report no hit outside the primitive's box: the
+ * rows and scalars are the fresh scene's, and the trees (another top level, mesh trees quantised for
+ * twice the reach) only decide which boxes a ray enters.  The reference's float sphere test does
+ * report such hits when r / distance falls to about 1e-4 (cancellation in its quadratic); which of
+ * those are found then depends on the boxes entered, in any two builds of a scene.  A scene that was never updated builds exactly as before. */
+int pt_scene_update_instances(pt_scene* scene, const pt_instance* instances, int64_t first, int64_t n);
 /* Device time of the last pt_scene_build_bvh (HIP events around the build's stream work). */
 int pt_scene_build_time(pt_scene* scene, double* ms);
 int pt_scene_bvh_info(pt_scene* scene, int* depth, int64_t* n_nodes, int64_t* device_bytes);
 /* The wide tree of the current build (0s before its first use): depth (levels), node slots,
  * build time in ms (wall time of the host build + upload, or of the device build when built at
  * first use; 0 when pt_scene_build_bvh built it -- then it is in pt_scene_build_time), source
- * (0 none, 1 host SAH, 2 device SAH or PLOC). */
+ * (0 none, 1 host SAH, 2 device SAH or PLOC, 3 an instanced scene's full host build of both
+ * levels, 4 an instanced scene's rebuild of the top level alone after pt_scene_update_instances). */
 int pt_scene_wide_info(pt_scene* scene, int* depth, int64_t* node_slots, double* build_ms, int* source);
 /* Download the LBVH in the reference's node layout (2n-1 nodes). */
 int pt_scene_download_bvh(pt_scene* scene, pt_bvh_node* nodes);

@@ -32,6 +32,7 @@
 
 #include "../host/pt_error.hpp"
 #include "../host/pt_host.hpp"
+#include "../host/pt_inst_dev.hpp"
 #include "../host/pt_wide8.hpp"
 #include "../host/pt_wide_dev.hpp"
 #include "pt.h"
@@ -3079,12 +3080,39 @@ struct StreamGuard {
     }
 };
 
+// A pair of events kept with their owner (a per-frame build times itself without creating any).
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair&) = delete;
+    EventPair& operator=(const EventPair&) = delete;
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+// On an early return (ok still false) waits for the stream's queued work, as StreamGuard does.
+struct StreamWait {
+    hipStream_t st;
+    bool ok = false;
+    explicit StreamWait(hipStream_t s) : st(s) {}
+    ~StreamWait() {
+        if (!ok) (void)hipStreamSynchronize(st);
+    }
+};
+
 int stackFor(int depth) {
     const int need = depth + 1;
     for (int s : {16, 24, 32, 48, 64, 80})
         if (need <= s) return s;
     return -1;
 }
+
+// A top-level leaf of an instanced scene: an instance entering its mesh's tree at `slot` (the mesh
+// tree's own slot numbering: 0 = its root; relocated with the tree).
+struct InstEntry {
+    uint32_t inst, mesh, slot;
+};
 
 }  // namespace
 
@@ -3106,7 +3134,7 @@ struct pt_scene {
     std::unique_ptr<pt::WideDevBuilder> wideDev;   // device build scratch (PT_BVH_WIDE_DEVICE), kept between builds
     bool wideReady = false;                 // the wide tree matches the current LBVH build
     bool updated = false;                   // pt_scene_update_objects was called: a dynamic scene
-    int wideSource = 0;                     // 1: host binned SAH, 2: device PLOC
+    int wideSource = 0;                     // 1: host binned SAH, 2: device SAH / PLOC, 3: instanced (full build), 4: instanced (top level only)
     int wideDepth = 0;
     int64_t wideNodes = 0;                  // node slots
     double wideBuildMs = 0.0;               // host build + upload, wall time
@@ -3122,6 +3150,24 @@ struct pt_scene {
     std::vector<pt_instance> inst;
     DevBuf winst;                           // per instance: world-to-object rows, {objBase, identity}
     int gBits = 0;                          // hit key = instance << gBits | shading index
+    // Instance updates (pt_scene_update_instances).  A full build of a dynamic scene lays the node
+    // array out for them -- the top level's region reserved at its upper bound, the mesh trees
+    // behind it, quantised for twice the current reach -- and keeps what the later builds need:
+    // they redo only the matrix-dependent work (rebuildInstancedTop).
+    bool instDynamic = false;               // instances were updated, or a build was given PT_BVH_WIDE_DEVICE
+    bool instPrepared = false;              // the members below match the node array
+    std::vector<double> instReach;          // per mesh: the reach its tree's planes were quantised for
+    std::vector<InstEntry> instEntries;     // the top level's entries, instances in order
+    std::vector<uint32_t> instMeshRoot;     // per mesh: its root's slot in the node array
+    uint32_t instTopCap = 0;                // node slots reserved for the top level
+    int instMaxDepthB = 0;                  // deepest mesh tree
+    DevBuf instM, instDesc, instSub, instOut;   // matrices, pt::InstBoxDesc, sub-root boxes; {instance boxes, entry boxes}
+    // the device top-level build's inputs (entry records {.., entry}, identity ranks, instEntries,
+    // instMeshRoot), its leaf-order entry records and the record kernel's error word
+    DevBuf instPrims, instRank, instEntriesDev, instMeshRootDev, instWprims, instErr;
+    EventPair instEvents;                   // the later builds' timing events, created once
+    std::vector<float> instHostM;           // their staging buffers, kept between builds
+    std::vector<double> instHostBox;
 };
 
 struct pt_film {
@@ -3226,11 +3272,6 @@ int buildWideDevice(pt_scene* s, hipStream_t st) {
 // array: the top level from slot 0, then the meshes' trees.  Shading records in object space, one
 // per mesh primitive (its shading index g); the hit key instance << gBits | g.
 int wideStackFor(int depth);
-// A top-level leaf: an instance entering its mesh's tree at `slot` (the mesh tree's own slot
-// numbering: 0 = its root; relocated with the tree).
-struct InstEntry {
-    uint32_t inst, mesh, slot;
-};
 struct InstRecCtx {
     const std::vector<std::array<float, 12>>* minv;
     const std::vector<uint8_t>* ident;   // 1: identity, 2: translation only, 0: general
@@ -3324,6 +3365,124 @@ void meshSubRootsBudget(const pt::Wide8& w, size_t budget, std::vector<SubRoot>&
 
 float mixLimit(double m);   // (below)
 
+// The world-to-object transform of one instance, in double and rounded to the fp32 rows the
+// kernels read, and its class (1: identity, 2: translation only, 0: general).  False for a singular
+// matrix (|det| <= 1e-30 or not finite).  The one place these are computed: a scene rebuilt after
+// pt_scene_update_instances and a fresh scene of the same matrices carry the same rows bit for bit.
+bool instanceInverse(const pt_instance& I, std::array<float, 12>& minv, std::array<double, 12>& w2o, uint8_t& cls) {
+    const double a[3][3] = {{I.m[0], I.m[1], I.m[2]}, {I.m[4], I.m[5], I.m[6]}, {I.m[8], I.m[9], I.m[10]}};
+    const double t[3] = {I.m[3], I.m[7], I.m[11]};
+    const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
+                       a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+    if (!(std::fabs(det) > 1e-30) || !std::isfinite(det)) return false;
+    double inv[3][3];
+    inv[0][0] = (a[1][1] * a[2][2] - a[1][2] * a[2][1]) / det;
+    inv[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) / det;
+    inv[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) / det;
+    inv[1][0] = (a[1][2] * a[2][0] - a[1][0] * a[2][2]) / det;
+    inv[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) / det;
+    inv[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) / det;
+    inv[2][0] = (a[1][0] * a[2][1] - a[1][1] * a[2][0]) / det;
+    inv[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) / det;
+    inv[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) / det;
+    bool id = true, lin = true;
+    for (int r = 0; r < 3; r++) {
+        const double it = -(inv[r][0] * t[0] + inv[r][1] * t[1] + inv[r][2] * t[2]);
+        for (int c = 0; c < 3; c++) {
+            minv[(size_t)(4 * r + c)] = (float)inv[r][c];
+            lin = lin && a[r][c] == (r == c ? 1.0 : 0.0);
+        }
+        minv[(size_t)(4 * r + 3)] = (float)it;
+        for (int c = 0; c < 3; c++) w2o[(size_t)(4 * r + c)] = inv[r][c];
+        w2o[(size_t)(4 * r + 3)] = it;
+        id = id && t[r] == 0.0;
+    }
+    id = id && lin;
+    cls = id ? 1 : (lin ? 2 : 0);
+    return true;
+}
+
+// Every instance's transform records: instanceInverse's, and the `winst` entry the kernels read
+// ({world-to-object rows, objBase, class}).
+struct InstRecords {
+    std::vector<std::array<float, 12>> minv;
+    std::vector<uint8_t> ident;   // 1: identity, 2: translation only, 0: general
+    std::vector<float> winst;
+    std::vector<std::array<double, 12>> w2o;   // world-to-object, double
+};
+int instanceRecords(const pt_scene* s, InstRecords& R) {
+    const int64_t ni = (int64_t)s->inst.size();
+    R.minv.resize((size_t)ni);
+    R.ident.assign((size_t)ni, 0);
+    R.winst.assign((size_t)std::max<int64_t>(1, ni) * 16, 0.0f);
+    R.w2o.resize((size_t)ni);
+    uint32_t objBase = 0;
+    for (int64_t i = 0; i < ni; i++) {
+        const pt_instance& I = s->inst[(size_t)i];
+        if (!instanceInverse(I, R.minv[(size_t)i], R.w2o[(size_t)i], R.ident[(size_t)i]))
+            return fail(PT_ERR_INVALID, "instanced scene: instance " + std::to_string(i) + " has a singular transform");
+        for (int k = 0; k < 12; k++) R.winst[(size_t)i * 16 + (size_t)k] = R.minv[(size_t)i][(size_t)k];
+        const uint32_t ob = objBase, idf = R.ident[(size_t)i];   // identity | translation only
+        std::memcpy(&R.winst[(size_t)i * 16 + 12], &ob, 4);
+        std::memcpy(&R.winst[(size_t)i * 16 + 13], &idf, 4);
+        objBase += (uint32_t)s->meshCount[(size_t)I.mesh];
+    }
+    return PT_OK;
+}
+
+// The scene scalars that follow from the world box (its centre and largest extent: instFar's
+// region, camFar; mixLim), and the reach of world ray origins into each mesh's object space.
+// Origins within kInstFarExt world extents of the centre (farther camera rays are moved up to the
+// world box first, renderKernelWF<.., INST>) map into object space within `reach` of the origin; a
+// mesh tree's plane quantum is taken against that reach, not the mesh's own size, so its outward
+// margin (wideHits) holds for every ray that enters it.
+struct InstScalars {
+    float ce[4];   // pt_scene::sceneCE
+    float mixLim;
+};
+void instanceScalars(const pt_scene* s, const double* wmn, const double* wmx, const std::vector<std::array<double, 12>>& w2o,
+                     InstScalars& out, std::vector<double>& reach) {
+    const int64_t ni = (int64_t)s->inst.size();
+    double wext = 0.0, wm = 0.0;
+    for (int a = 0; a < 3; a++) {
+        out.ce[a] = (float)(0.5 * (wmn[a] + wmx[a]));
+        wext = std::max(wext, wmx[a] - wmn[a]);
+        wm = std::max({wm, std::fabs(wmn[a]), std::fabs(wmx[a]), wmx[a] - wmn[a]});
+    }
+    out.ce[3] = std::nextafter((float)wext, INFINITY);
+    out.mixLim = mixLimit(wm);
+    reach.assign(s->meshFirst.size(), 0.0);
+    for (int64_t i = 0; i < ni; i++) {
+        const std::array<double, 12>& W = w2o[(size_t)i];
+        double r = 0.0;
+        for (int c = 0; c < 8; c++) {   // corners of the cube of half-size kInstFarExt world extents (+ 1 %)
+            const double h = 1.01 * kInstFarExt * wext;
+            const double p[3] = {0.5 * (wmn[0] + wmx[0]) + ((c & 1) ? h : -h), 0.5 * (wmn[1] + wmx[1]) + ((c & 2) ? h : -h),
+                                 0.5 * (wmn[2] + wmx[2]) + ((c & 4) ? h : -h)};
+            for (int a = 0; a < 3; a++)
+                r = std::max(r, std::fabs(W[(size_t)(4 * a)] * p[0] + W[(size_t)(4 * a + 1)] * p[1] +
+                                          W[(size_t)(4 * a + 2)] * p[2] + W[(size_t)(4 * a + 3)]));
+        }
+        const int m = s->inst[(size_t)i].mesh;
+        reach[(size_t)m] = std::max(reach[(size_t)m], r);
+    }
+}
+
+// The top level: an 8-wide tree over the entries' world boxes, one entry per leaf, its leaves
+// turned into instance records (the mesh tree's base slot is added by the caller).
+bool instanceTop(const InstRecords& rec, const std::vector<InstEntry>& entries, const float* eboxes, pt::Wide8& top,
+                 std::string& err) {
+    std::vector<uint32_t> iprims(entries.size() * pt::kW8PrimDwords, 0u);
+    for (size_t e = 0; e < entries.size(); e++) iprims[e * pt::kW8PrimDwords + 7] = (uint32_t)e;
+    if (!pt::buildWide8Leaf(iprims.data(), eboxes, nullptr, (int64_t)entries.size(), 1, top, err)) return false;
+    InstRecCtx ctx{&rec.minv, &rec.ident, &entries};
+    return pt::instanceLeaves(top, instanceOfRecord, writeInstanceRecord, &ctx, err);
+}
+// Node slots of a top level over n entries, at most: every node has one block of 8 child slots
+// (internal children and instance records share it) and stands for at least one internal node of
+// the binary tree, of which there are n - 1.
+int64_t instanceTopSlots(int64_t n) { return 1 + 8 * std::max<int64_t>(1, n - 1); }
+
 int buildInstanced(pt_scene* s) {
     const auto t0 = std::chrono::steady_clock::now();
     const int nm = (int)s->meshFirst.size();
@@ -3398,51 +3557,18 @@ int buildInstanced(pt_scene* s) {
         return fail(PT_ERR_INVALID, "instanced scene: too many instances for the hit key (instance << " +
                                         std::to_string(gBits) + " | primitive)");
     // instances: world-to-object transforms, world boxes (every mesh vertex transformed, in double)
-    std::vector<std::array<float, 12>> minv((size_t)ni);
-    std::vector<uint8_t> ident((size_t)ni, 0);
+    InstRecords rec;
+    int rc = instanceRecords(s, rec);
+    if (rc) return rc;
+    const std::vector<float>& winst = rec.winst;
+    const std::vector<std::array<double, 12>>& w2o = rec.w2o;
     std::vector<std::array<double, 6>> ibox((size_t)ni);   // world box of each instance
     std::vector<uint32_t> used;
-    std::vector<float> winst((size_t)std::max<int64_t>(1, ni) * 16, 0.0f);
-    std::vector<std::array<double, 12>> w2o((size_t)ni);   // world-to-object, double
     double wmn[3] = {INFINITY, INFINITY, INFINITY}, wmx[3] = {-INFINITY, -INFINITY, -INFINITY};   // the world box
-    uint32_t objBase = 0;
     for (int64_t i = 0; i < ni; i++) {
         const pt_instance& I = s->inst[(size_t)i];
         const double a[3][3] = {{I.m[0], I.m[1], I.m[2]}, {I.m[4], I.m[5], I.m[6]}, {I.m[8], I.m[9], I.m[10]}};
         const double t[3] = {I.m[3], I.m[7], I.m[11]};
-        const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
-                           a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
-        if (!(std::fabs(det) > 1e-30) || !std::isfinite(det))
-            return fail(PT_ERR_INVALID, "instanced scene: instance " + std::to_string(i) + " has a singular transform");
-        double inv[3][3];
-        inv[0][0] = (a[1][1] * a[2][2] - a[1][2] * a[2][1]) / det;
-        inv[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) / det;
-        inv[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) / det;
-        inv[1][0] = (a[1][2] * a[2][0] - a[1][0] * a[2][2]) / det;
-        inv[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) / det;
-        inv[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) / det;
-        inv[2][0] = (a[1][0] * a[2][1] - a[1][1] * a[2][0]) / det;
-        inv[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) / det;
-        inv[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) / det;
-        bool id = true, lin = true;
-        for (int r = 0; r < 3; r++) {
-            const double it = -(inv[r][0] * t[0] + inv[r][1] * t[1] + inv[r][2] * t[2]);
-            for (int c = 0; c < 3; c++) {
-                minv[(size_t)i][(size_t)(4 * r + c)] = (float)inv[r][c];
-                lin = lin && a[r][c] == (r == c ? 1.0 : 0.0);
-            }
-            minv[(size_t)i][(size_t)(4 * r + 3)] = (float)it;
-            for (int c = 0; c < 3; c++) w2o[(size_t)i][(size_t)(4 * r + c)] = inv[r][c];
-            w2o[(size_t)i][(size_t)(4 * r + 3)] = it;
-            id = id && t[r] == 0.0;
-        }
-        id = id && lin;
-        ident[(size_t)i] = id ? 1 : (lin ? 2 : 0);
-        for (int k = 0; k < 12; k++) winst[(size_t)i * 16 + (size_t)k] = minv[(size_t)i][(size_t)k];
-        uint32_t ob = objBase, idf = id ? 1u : lin ? 2u : 0u;   // identity | translation only
-        std::memcpy(&winst[(size_t)i * 16 + 12], &ob, 4);
-        std::memcpy(&winst[(size_t)i * 16 + 13], &idf, 4);
-        objBase += (uint32_t)s->meshCount[(size_t)I.mesh];
         // world box of the instance
         const int64_t first = s->meshFirst[(size_t)I.mesh], n = s->meshCount[(size_t)I.mesh];
         if (n == 0) continue;
@@ -3473,35 +3599,15 @@ int buildInstanced(pt_scene* s) {
         used.push_back((uint32_t)i);
     }
     if (used.empty()) return fail(PT_ERR_STATE, "instanced scene: no instance of a non-empty mesh");
-    // The world box (its centre and largest extent: instFar's region, camFar), and the reach of
-    // world ray origins into each mesh's object space.  Origins within kInstFarExt world extents of
-    // the centre (farther camera rays are moved up to the world box first, renderKernelWF<.., INST>)
-    // map into object space within `reach` of the origin; the mesh tree's plane quantum is taken
-    // against that reach, not the mesh's own size, so its outward margin (wideHits) holds for
-    // every ray that enters it.
-    double wext = 0.0, wm = 0.0;
-    for (int a = 0; a < 3; a++) {
-        s->sceneCE[a] = (float)(0.5 * (wmn[a] + wmx[a]));
-        wext = std::max(wext, wmx[a] - wmn[a]);
-        wm = std::max({wm, std::fabs(wmn[a]), std::fabs(wmx[a]), wmx[a] - wmn[a]});
-    }
-    s->sceneCE[3] = std::nextafter((float)wext, INFINITY);
-    s->mixLim = mixLimit(wm);
-    std::vector<double> reach((size_t)nm, 0.0);
-    for (int64_t i = 0; i < ni; i++) {
-        const std::array<double, 12>& W = w2o[(size_t)i];
-        double r = 0.0;
-        for (int c = 0; c < 8; c++) {   // corners of the cube of half-size kInstFarExt world extents (+ 1 %)
-            const double h = 1.01 * kInstFarExt * wext;
-            const double p[3] = {0.5 * (wmn[0] + wmx[0]) + ((c & 1) ? h : -h), 0.5 * (wmn[1] + wmx[1]) + ((c & 2) ? h : -h),
-                                 0.5 * (wmn[2] + wmx[2]) + ((c & 4) ? h : -h)};
-            for (int a = 0; a < 3; a++)
-                r = std::max(r, std::fabs(W[(size_t)(4 * a)] * p[0] + W[(size_t)(4 * a + 1)] * p[1] +
-                                          W[(size_t)(4 * a + 2)] * p[2] + W[(size_t)(4 * a + 3)]));
-        }
-        const int m = s->inst[(size_t)i].mesh;
-        reach[(size_t)m] = std::max(reach[(size_t)m], r);
-    }
+    // The scene scalars and each mesh's reach.  A dynamic scene's mesh trees are quantised for twice
+    // the reach, so that ordinary motion stays within it and the later builds keep the trees.
+    std::vector<double> reach;
+    InstScalars sc;
+    instanceScalars(s, wmn, wmx, w2o, sc, reach);
+    for (int a = 0; a < 4; a++) s->sceneCE[a] = sc.ce[a];
+    s->mixLim = sc.mixLim;
+    if (s->instDynamic)
+        for (double& r : reach) r *= 2.0;
     for (int m = 0; m < nm; m++) {
         const int64_t n = s->meshCount[(size_t)m];
         if (n > 0 && !pt::buildWide8(meshPrims[(size_t)m].data(), meshBoxes[(size_t)m].data(), meshRank[(size_t)m].data(),
@@ -3522,11 +3628,8 @@ int buildInstanced(pt_scene* s) {
         if (sub[(size_t)m].size() == 1) sub[(size_t)m].clear();   // (the root itself)
     }
     std::vector<InstEntry> entries;
-    std::vector<uint32_t> iprims;
     std::vector<float> iboxes;
     auto addEntry = [&](uint32_t i, uint32_t mesh, uint32_t slot, const double* b) {
-        iprims.resize(iprims.size() + pt::kW8PrimDwords, 0u);
-        iprims[iprims.size() - pt::kW8PrimDwords + 7] = (uint32_t)entries.size();
         for (int r = 0; r < 3; r++) iboxes.push_back(std::nextafter((float)b[r], -INFINITY));
         for (int r = 0; r < 3; r++) iboxes.push_back(std::nextafter((float)b[3 + r], INFINITY));
         entries.push_back({i, mesh, slot});
@@ -3559,12 +3662,18 @@ int buildInstanced(pt_scene* s) {
         }
     }
     pt::Wide8 top;
-    if (!pt::buildWide8Leaf(iprims.data(), iboxes.data(), nullptr, (int64_t)entries.size(), 1, top, err))
-        return fail(PT_ERR_STATE, err);
-    InstRecCtx ctx{&minv, &ident, &entries};
-    if (!pt::instanceLeaves(top, instanceOfRecord, writeInstanceRecord, &ctx, err)) return fail(PT_ERR_STATE, err);
-    // layout: the top level from slot 0, then each mesh's tree (child and primitive bases relocated)
-    const uint32_t topSlots = (uint32_t)(top.nodes.size() / pt::kW8NodeDwords);
+    if (!instanceTop(rec, entries, iboxes.data(), top, err)) return fail(PT_ERR_STATE, err);
+    // layout: the top level from slot 0, then each mesh's tree (child and primitive bases relocated).
+    // A dynamic scene reserves the top level's region at its upper bound for this number of entries
+    // (its slot count changes with the matrices), so that later builds rewrite that region alone.
+    uint32_t topSlots = (uint32_t)(top.nodes.size() / pt::kW8NodeDwords);
+    if (s->instDynamic) {
+        const int64_t cap = instanceTopSlots((int64_t)entries.size());
+        if ((int64_t)topSlots > cap || cap >= ((int64_t)1 << 24))
+            return fail(PT_ERR_STATE, "instanced BVH: top level beyond its reserved node slots");
+        topSlots = (uint32_t)cap;
+        top.nodes.resize((size_t)cap * pt::kW8NodeDwords, 0u);
+    }
     std::vector<uint32_t> meshRoot((size_t)nm, 0u);
     uint32_t nodeBase = topSlots, primBase = 0;
     for (int m = 0; m < nm; m++) {
@@ -3586,7 +3695,6 @@ int buildInstanced(pt_scene* s) {
     }
     if (prims.empty()) prims.assign(pt::kW8PrimDwords, 0u);
     if (shade.empty()) shade.assign(12, 0u);
-    int rc;
     if ((rc = devReserve(s->wide, nodes.size() * 4)) || (rc = devReserve(s->wprims, prims.size() * 4)) ||
         (rc = devReserve(s->wshade, shade.size() * 4)) || (rc = devReserve(s->winst, winst.size() * 4)))
         return rc;
@@ -3600,11 +3708,160 @@ int buildInstanced(pt_scene* s) {
     s->wideSource = 3;
     s->wideReady = true;
     s->deviceBytes = nodes.size() * 4 + prims.size() * 4 + shade.size() * 4 + winst.size() * 4 + (size_t)s->nmat * 32;
+    s->instPrepared = false;
+    if (s->instDynamic) {   // what the later builds need (rebuildInstancedTop)
+        std::vector<pt::InstBoxDesc> desc((size_t)ni);
+        std::vector<int32_t> subFirst((size_t)nm, -1);
+        std::vector<double> subBoxes;
+        for (int m = 0; m < nm; m++) {
+            if (sub[(size_t)m].empty()) continue;
+            subFirst[(size_t)m] = (int32_t)(subBoxes.size() / 6);
+            for (const SubRoot& r : sub[(size_t)m]) subBoxes.insert(subBoxes.end(), r.box, r.box + 6);
+        }
+        size_t e = 0;
+        for (int64_t i = 0; i < ni; i++) {
+            const int mesh = s->inst[(size_t)i].mesh;
+            pt::InstBoxDesc& D = desc[(size_t)i];
+            D = pt::InstBoxDesc{};
+            D.objFirst = (int32_t)s->meshFirst[(size_t)mesh];
+            D.objCount = (int32_t)s->meshCount[(size_t)mesh];
+            D.entryFirst = (int32_t)e;
+            D.subFirst = subFirst[(size_t)mesh];
+            D.entryCount = D.objCount == 0 ? 0 : (D.subFirst < 0 ? 1 : (int32_t)sub[(size_t)mesh].size());
+            e += (size_t)D.entryCount;
+        }
+        if (e != entries.size()) return fail(PT_ERR_STATE, "instanced BVH: entry count mismatch");
+        if (subBoxes.empty()) subBoxes.assign(6, 0.0);
+        const size_t outBytes = (size_t)ni * 48 + entries.size() * 24;
+        if ((rc = devReserve(s->instM, (size_t)ni * 48)) || (rc = devReserve(s->instDesc, desc.size() * sizeof(pt::InstBoxDesc))) ||
+            (rc = devReserve(s->instSub, subBoxes.size() * 8)) || (rc = devReserve(s->instOut, outBytes)))
+            return rc;
+        HIP_TRY(hipMemcpy(s->instDesc.p, desc.data(), desc.size() * sizeof(pt::InstBoxDesc), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->instSub.p, subBoxes.data(), subBoxes.size() * 8, hipMemcpyHostToDevice));
+        const size_t ne = entries.size();
+        std::vector<uint32_t> eprims(ne * pt::kW8PrimDwords, 0u), erank(ne), eflat(ne * 3), eroot((size_t)std::max(1, nm), 0u);
+        for (size_t k = 0; k < ne; k++) {
+            eprims[k * pt::kW8PrimDwords + 7] = (uint32_t)k;
+            erank[k] = (uint32_t)k;
+            eflat[3 * k] = entries[k].inst; eflat[3 * k + 1] = entries[k].mesh; eflat[3 * k + 2] = entries[k].slot;
+        }
+        for (int m = 0; m < nm; m++) eroot[(size_t)m] = meshRoot[(size_t)m];
+        if ((rc = devReserve(s->instPrims, eprims.size() * 4)) || (rc = devReserve(s->instRank, erank.size() * 4)) ||
+            (rc = devReserve(s->instEntriesDev, eflat.size() * 4)) || (rc = devReserve(s->instMeshRootDev, eroot.size() * 4)) ||
+            (rc = devReserve(s->instWprims, eprims.size() * 4)) || (rc = devReserve(s->instErr, 16)))
+            return rc;
+        HIP_TRY(hipMemcpy(s->instPrims.p, eprims.data(), eprims.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->instRank.p, erank.data(), erank.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->instEntriesDev.p, eflat.data(), eflat.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->instMeshRootDev.p, eroot.data(), eroot.size() * 4, hipMemcpyHostToDevice));
+        if (!s->wideDev) s->wideDev.reset(new pt::WideDevBuilder);
+        HIP_TRY(s->wideDev->reserveTop((int64_t)ne));   // the later builds allocate nothing
+        s->instReach = reach;
+        s->instEntries = entries;
+        s->instMeshRoot = meshRoot;
+        s->instTopCap = topSlots;
+        s->instMaxDepthB = maxDepthB;
+        s->deviceBytes += (size_t)ni * 48 + desc.size() * sizeof(pt::InstBoxDesc) + subBoxes.size() * 8 + outBytes +
+                          2 * eprims.size() * 4 + erank.size() * 4 + eflat.size() * 4 + eroot.size() * 4;
+        s->instPrepared = true;
+    }
     s->wideBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     s->buildMs = s->wideBuildMs;
     s->depth = 0;
     if (wideStackFor(s->wideDepth) < 0) return fail(PT_ERR_STATE, "instanced BVH too deep");
     s->built = true;
+    return PT_OK;
+}
+
+// A dynamic instanced scene's later builds: only what depends on the matrices, on the device, on
+// `st`.  The world-to-object rows (instanceRecords: the full build's code, 64 B per instance) and
+// the matrices are uploaded; csrc/pt_inst_build.hip computes the instances' exact world boxes and
+// the entries' boxes; the instances' boxes (48 B each) are read back for the world box, from which
+// the host takes the scene scalars and each mesh's reach exactly as the full build does
+// (instanceScalars); then the top level is built in its reserved, zeroed region by the wide
+// builder's SAH and collapse stages with one entry per leaf (WideDevBuilder::buildTop) and its
+// leaves become instance records (pt::instanceRecords).  The mesh trees, primitive and shading
+// records are not touched and nothing is allocated.  The scene's scalars are committed only when
+// the build has succeeded.
+// *done = false (and PT_OK): a mesh's new reach exceeds the reach its tree was quantised for --
+// the caller runs the full build.
+int rebuildInstancedTop(pt_scene* s, hipStream_t st, bool* done) {
+    const auto t0 = std::chrono::steady_clock::now();
+    *done = false;
+    const int64_t ni = (int64_t)s->inst.size();
+    const size_t ne = s->instEntries.size();
+    InstRecords rec;
+    int rc = instanceRecords(s, rec);
+    if (rc) return rc;
+    std::vector<float>& hm = s->instHostM;
+    std::vector<double>& ibox = s->instHostBox;
+    hm.resize((size_t)ni * 12);
+    ibox.resize((size_t)ni * 6);
+    for (int64_t i = 0; i < ni; i++) std::memcpy(&hm[(size_t)i * 12], s->inst[(size_t)i].m, 48);
+    if (!s->instEvents.e0) HIP_TRY(hipEventCreate(&s->instEvents.e0));
+    if (!s->instEvents.e1) HIP_TRY(hipEventCreate(&s->instEvents.e1));
+    struct { hipEvent_t e0, e1; } ev{s->instEvents.e0, s->instEvents.e1};
+    StreamWait guard(st);
+    HIP_TRY(hipEventRecord(ev.e0, st));
+    HIP_TRY(hipMemcpyAsync(s->instM.p, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->winst.p, rec.winst.data(), rec.winst.size() * 4, hipMemcpyHostToDevice, st));
+    double* dibox = s->instOut.as<double>();
+    float* debox = reinterpret_cast<float*>(dibox + (size_t)ni * 6);
+    const pt::InstBoxIn in{s->dobjs.as<pt_object>(), s->instM.as<float>(), s->instDesc.as<pt::InstBoxDesc>(),
+                           s->instSub.as<double>(), ni};
+    HIP_TRY(pt::instanceBoxes(in, dibox, debox, st));
+    HIP_TRY(hipMemcpyAsync(ibox.data(), dibox, (size_t)ni * 48, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // the world box over the instances of non-empty meshes, from it the scalars and the new reach
+    double wmn[3] = {INFINITY, INFINITY, INFINITY}, wmx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t i = 0; i < ni; i++) {
+        if (s->meshCount[(size_t)s->inst[(size_t)i].mesh] == 0) continue;
+        for (int r = 0; r < 3; r++) {
+            wmn[r] = std::min(wmn[r], ibox[(size_t)i * 6 + (size_t)r]);
+            wmx[r] = std::max(wmx[r], ibox[(size_t)i * 6 + 3 + (size_t)r]);
+        }
+    }
+    InstScalars sc;
+    std::vector<double> reach;
+    instanceScalars(s, wmn, wmx, rec.w2o, sc, reach);
+    for (size_t m = 0; m < reach.size(); m++)
+        if (!(reach[m] <= s->instReach[m])) {
+            guard.ok = true;
+            return PT_OK;
+        }
+    // the top level, in its reserved region
+    HIP_TRY(hipMemsetAsync(s->wide.p, 0, (size_t)s->instTopCap * pt::kW8NodeDwords * 4, st));
+    HIP_TRY(hipMemsetAsync(s->instErr.p, 0, 4, st));
+    std::string err;
+    int topDepth = 0;
+    int64_t topSlots = 0;
+    const hipError_t e = s->wideDev->buildTop(debox, (int64_t)ne, s->instPrims.as<float4>(), s->instRank.as<uint32_t>(),
+                                              s->wide.as<uint32_t>(), s->instWprims.as<uint32_t>(), s->instTopCap, st, err,
+                                              topDepth, topSlots);
+    if (e != hipSuccess) return fail(err.empty() ? PT_ERR_HIP : PT_ERR_STATE, err.empty() ? hipGetErrorString(e) : err);
+    if (topSlots > (int64_t)s->instTopCap) return fail(PT_ERR_STATE, "instanced BVH: top level beyond its reserved node slots");
+    HIP_TRY(pt::instanceRecords(s->wide.as<uint32_t>(), (uint32_t)topSlots, s->instWprims.as<uint32_t>(),
+                                s->instEntriesDev.as<uint32_t>(), (uint32_t)ne, s->winst.as<float>(),
+                                s->instMeshRootDev.as<uint32_t>(), s->instErr.as<uint32_t>(), st));
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, s->instErr.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(ev.e1, st));
+    HIP_TRY(hipEventSynchronize(ev.e1));
+    guard.ok = true;
+    if (bad) return fail(PT_ERR_STATE, "instanced BVH: malformed top level (flags " + std::to_string(bad) + ")");
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    for (int a = 0; a < 4; a++) s->sceneCE[a] = sc.ce[a];
+    s->mixLim = sc.mixLim;
+    s->wideDepth = topDepth + 1 + s->instMaxDepthB + 1;
+    s->wideSource = 4;
+    s->wideReady = true;
+    s->buildMs = (double)ms;
+    s->wideBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    s->depth = 0;
+    if (wideStackFor(s->wideDepth) < 0) return fail(PT_ERR_STATE, "instanced BVH too deep");
+    s->built = true;
+    *done = true;
     return PT_OK;
 }
 
@@ -3931,14 +4188,48 @@ int pt_scene_update_objects(pt_scene* s, const pt_object* objs, int64_t first, i
     return PT_OK;
 }
 
+int pt_scene_update_instances(pt_scene* s, const pt_instance* inst, int64_t first, int64_t n) {
+    // (the arguments that need no look at the scene first)
+    if (!s || first < 0 || n < 0 || (n > 0 && !inst)) return fail(PT_ERR_INVALID, "pt_scene_update_instances: bad argument");
+    if (!s->instanced) return fail(PT_ERR_INVALID, "pt_scene_update_instances: not an instanced scene");
+    const int64_t ni = (int64_t)s->inst.size();
+    if (first > ni || n > ni - first)
+        return fail(PT_ERR_INVALID, "pt_scene_update_instances: range outside the scene's " + std::to_string(ni) + " instances");
+    for (int64_t i = 0; i < n; i++) {
+        const std::string who = "pt_scene_update_instances: instance " + std::to_string(first + i);
+        if (inst[i].mesh != s->inst[(size_t)(first + i)].mesh)
+            return fail(PT_ERR_INVALID, who + " changes its mesh (the object numbering depends on it: create a new scene)");
+        for (int k = 0; k < 12; k++)
+            if (!std::isfinite(inst[i].m[k])) return fail(PT_ERR_INVALID, who + " has a non-finite matrix entry");
+        std::array<float, 12> minv;
+        std::array<double, 12> w2o;
+        uint8_t cls;
+        if (!instanceInverse(inst[i], minv, w2o, cls)) return fail(PT_ERR_INVALID, who + " has a singular transform");
+    }
+    if (n == 0) return PT_OK;
+    std::copy(inst, inst + n, s->inst.begin() + first);
+    s->built = false;        // the top level no longer matches the matrices: rebuild before rendering
+    s->instDynamic = true;   // from now on builds keep the mesh trees (pt_scene_build_bvh)
+    return PT_OK;
+}
+
 int pt_scene_build_bvh(pt_scene* s, int flags) { return pt_scene_build_bvh_ex(s, flags, nullptr); }
 
 int pt_scene_build_bvh_ex(pt_scene* s, int flags, void* stream) {
     if (!s) return fail(PT_ERR_INVALID, "pt_scene_build_bvh: null scene");
     int rc = setDevice(s->device);
     if (rc) return rc;
-    if (s->instanced) {   // the two-level tree, on the host (flags: the LBVH's, not applicable)
+    if (s->instanced) {   // the two-level tree (flags: the LBVH's do not apply)
         s->built = false;
+        // PT_BVH_WIDE_DEVICE: lay the scene out for instance updates.  A dynamic scene's first build
+        // is the full host build in that layout; later ones redo the matrix-dependent work alone,
+        // unless a mesh's reach has outgrown its tree (then the full build again).
+        if (flags & PT_BVH_WIDE_DEVICE) s->instDynamic = true;
+        if (s->instDynamic && s->instPrepared) {
+            bool done = false;
+            if ((rc = rebuildInstancedTop(s, static_cast<hipStream_t>(stream), &done))) return rc;
+            if (done) return PT_OK;
+        }
         return buildInstanced(s);
     }
     const int64_t n = s->nobj;
@@ -4468,7 +4759,7 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
         for (int a = 0; a < 3; a++)
             m = std::max(m, std::fabs((double)cam->origin[a] - (double)s->sceneCE[a]) +
                                 (double)cam->lens_radius * (std::fabs((double)cam->right[a]) + std::fabs((double)cam->up[a])));
-        P.camFar = !(m <= (s->wideSource == 3 ? (double)kInstFarExt : (double)kWideFarExt) * (double)s->sceneCE[3]) ? 1 : 0;
+        P.camFar = !(m <= (s->instanced ? (double)kInstFarExt : (double)kWideFarExt) * (double)s->sceneCE[3]) ? 1 : 0;
     }
     // Defaults swept on C3 (tools/ab_env.py): sample mode is throughput-bound and prefers full
     // LEAF / SHADE steps.  Compat mode on the binary tree is bound by its slowest pixels' sequential

@@ -337,7 +337,9 @@ __device__ int collapse(const Tree& T, uint32_t root, uint32_t ch[8], bool grp[8
 
 __global__ void setRootKernel(const uint32_t* __restrict__ cid, uint2* items) { items[0] = make_uint2(cid[0], 0u); }
 
-__global__ void wideCountKernel(Tree T, const uint2* __restrict__ items, int m, uint4* cnt) {
+// everyBlock: a node gets its block of 8 child slots even when all its children are leaves (the top
+// level of an instanced scene: its leaves become instance records in those slots).
+__global__ void wideCountKernel(Tree T, const uint2* __restrict__ items, int m, uint32_t everyBlock, uint4* cnt) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     uint32_t ch[8];
@@ -348,12 +350,12 @@ __global__ void wideCountKernel(Tree T, const uint2* __restrict__ items, int m, 
         if (grp[j]) prims += T.count(ch[j]);
         else internal++;
     }
-    cnt[i] = make_uint4(internal ? 8u : 0u, prims, internal, 0u);
+    cnt[i] = make_uint4(internal || everyBlock ? 8u : 0u, prims, internal, 0u);
 }
 
 __global__ void wideWriteKernel(Tree T, const uint2* __restrict__ items, int m, const uint4* __restrict__ cnt,
                                 const uint4* __restrict__ ofs, uint32_t nodeBase, uint32_t primBase, uint32_t slotCap,
-                                const uint32_t* __restrict__ rootCid, const float4* __restrict__ prims,
+                                uint32_t everyBlock, const uint32_t* __restrict__ rootCid, const float4* __restrict__ prims,
                                 const uint32_t* __restrict__ rank, uint32_t* nodes, uint4* wprims, uint2* next,
                                 uint32_t* misc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -372,7 +374,8 @@ __global__ void wideWriteKernel(Tree T, const uint2* __restrict__ items, int m, 
     const uint32_t childBase = nodeBase + o.x, myPrims = primBase + o.y;
     bool anyInternal = false;
     for (int j = 0; j < c; j++) anyInternal |= !grp[j];
-    if (item.y >= slotCap || (anyInternal && childBase + 8u > slotCap)) {
+    const bool block = anyInternal || everyBlock != 0u;
+    if (item.y >= slotCap || (block && childBase + 8u > slotCap)) {
         atomicOr(misc + kMiscErr, 1u);
         return;
     }
@@ -511,7 +514,7 @@ __global__ void wideWriteKernel(Tree T, const uint2* __restrict__ items, int m, 
         }
     }
     R[3] = exps;
-    R[4] = anyInternal ? childBase : 0u;
+    R[4] = block ? childBase : 0u;
     R[5] = myPrims;
     R[6] = meta[0];
     R[7] = meta[1];
@@ -1080,8 +1083,8 @@ struct WaveLds {   // one wave's task: primitives by local index, the axis order
 // children are again segments in all three orders.
 __global__ __launch_bounds__(256) void sahWaveKernel(const SahTask* __restrict__ tasks, int ntask, const uint32_t* __restrict__ idBase,
                                                      const uint32_t* __restrict__ ref, const float4* __restrict__ cen,
-                                                     const float* __restrict__ leafBoxes, uint32_t n, float trav, float4* pbox,
-                                                     uint2* pchild, uint32_t* cnt) {
+                                                     const float* __restrict__ leafBoxes, uint32_t n, float trav, int maxGroup,
+                                                     float4* pbox, uint2* pchild, uint32_t* cnt) {
     __shared__ WaveLds lds[4];
     const int lane = (int)(threadIdx.x & 63);
     const int ti = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -1153,7 +1156,7 @@ __global__ __launch_bounds__(256) void sahWaveKernel(const SahTask* __restrict__
             axis = 0;
             lc = sc / 2;
         }
-        const bool leaf = active && sc <= kMaxGroup && (float)sc * segArea <= trav * segArea + bestCost;
+        const bool leaf = active && sc <= maxGroup && (float)sc * segArea <= trav * segArea + bestCost;
         // a leaf group: node over two primitives, or node(p0, inner(p1, p2))
         const int j1 = __shfl(idx[0], (sb + 1) & 63), j2 = __shfl(idx[0], (sb + 2) & 63);
         const uint64_t m3 = __ballot(leaf && lane == sb && sc == 3);
@@ -1256,8 +1259,7 @@ hipError_t WideDevBuilder::reserve(Buf& b, size_t bytes) {
 
 // Step 2 by SAH: large tasks level by level (one host read per level: the task list, to map
 // blocks to tasks), then every wave-sized task in one launch.
-hipError_t WideDevBuilder::buildSah(const WideDevIn& in, hipStream_t st, float trav, std::string& err) {
-    const int64_t n = in.n;
+hipError_t WideDevBuilder::reserveSah(int64_t n) {
     const size_t nn = (size_t)n;
     const size_t largeCap = nn / (kWaveTask + 1) + 2, smallCap = nn / 2 + 2, multiCap = nn / kChunk + 2;
     const size_t blockCap = nn / kChunk + largeCap + 1;
@@ -1274,6 +1276,15 @@ hipError_t WideDevBuilder::buildSah(const WideDevIn& in, hipStream_t st, float t
     WB_TRY(reserve(sahBlkR_, (blockCap > smallCap ? blockCap : smallCap) * 4));   // block counts, then wave-task node counts
     WB_TRY(reserve(sahBlkO_, (blockCap > smallCap ? blockCap : smallCap) * 4));
     WB_TRY(reserve(sahCnt_, (kSahWords + 12) * 4));
+    return hipSuccess;
+}
+
+hipError_t WideDevBuilder::buildSah(const WideDevIn& in, hipStream_t st, float trav, int maxGroup, std::string& err) {
+    const int64_t n = in.n;
+    const size_t nn = (size_t)n;
+    const size_t largeCap = nn / (kWaveTask + 1) + 2, smallCap = nn / 2 + 2, multiCap = nn / kChunk + 2;
+    const size_t blockCap = nn / kChunk + largeCap + 1;
+    WB_TRY(reserveSah(n));
     float4* pbox = static_cast<float4*>(pbox_.p);
     uint2* pchild = static_cast<uint2*>(pchild_.p);
     float4* cen = static_cast<float4*>(sahCen_.p);
@@ -1367,8 +1378,8 @@ hipError_t WideDevBuilder::buildSah(const WideDevIn& in, hipStream_t st, float t
         sahWaveCountKernel<<<blocks(ns, tb), tb, 0, st>>>(small, ns, blkR);
         WB_TRY(check("wave counts"));
         WB_TRY(exclusiveScanU32(scanTemp_.p, blkR, blkO, (size_t)ns, st));
-        sahWaveKernel<<<blocks(ns, 4), 256, 0, st>>>(small, ns, blkO, ref, cen, in.leafBoxes, (uint32_t)n, trav, pbox, pchild,
-                                                     cnt);
+        sahWaveKernel<<<blocks(ns, 4), 256, 0, st>>>(small, ns, blkO, ref, cen, in.leafBoxes, (uint32_t)n, trav, maxGroup, pbox,
+                                                     pchild, cnt);
         WB_TRY(check("wave tasks"));
     }
     if (!c[kSahSmall]) WB_TRY(hipMemcpyAsync(cnt + kSahTotal, cnt + kSahNodes, 4, hipMemcpyDeviceToDevice, st));
@@ -1383,15 +1394,7 @@ hipError_t WideDevBuilder::buildSah(const WideDevIn& in, hipStream_t st, float t
     return hipSuccess;
 }
 
-hipError_t WideDevBuilder::build(const WideDevIn& in, WideDevOut& out, hipStream_t st, std::string& err) {
-    const int64_t n = in.n;
-    out.depth = 0;
-    out.slots = 0;
-    if (n <= 0) return hipSuccess;
-    if (n >= ((int64_t)1 << 26)) {
-        err = "wide BVH (device): more than 2^26 primitives";
-        return hipErrorInvalidValue;
-    }
+hipError_t WideDevBuilder::reserveScratch(int64_t n) {
     const size_t nn = (size_t)n, nodesAll = 2 * nn;
     WB_TRY(reserve(pbox_, nodesAll * 32));
     WB_TRY(reserve(pchild_, nn * 8));
@@ -1406,7 +1409,98 @@ hipError_t WideDevBuilder::build(const WideDevIn& in, WideDevOut& out, hipStream
     WB_TRY(reserve(ofs_, nn * 16));
     WB_TRY(reserve(misc_, kMiscWords * 4));
     const size_t tb1 = scanScratchBytesU32(nn), tb2 = scanScratchBytesU3(nn);
-    WB_TRY(reserve(scanTemp_, tb1 > tb2 ? tb1 : tb2));
+    return reserve(scanTemp_, tb1 > tb2 ? tb1 : tb2);
+}
+
+// Step 3: collapse + quantisation, level by level, from the binary tree in pbox_ / pchild_ whose
+// root id is at `rootCid`.
+hipError_t WideDevBuilder::collapseLevels(int64_t n, const uint32_t* rootCid, uint32_t slotCap, uint32_t everyBlock,
+                                          const float4* prims, const uint32_t* rank, uint32_t* nodes, uint32_t* wprims,
+                                          hipStream_t st, std::string& err, int& depth, int64_t& slots) {
+    uint32_t* misc = static_cast<uint32_t*>(misc_.p);
+    const unsigned tb = 256;
+    const Tree T{static_cast<float4*>(pbox_.p), static_cast<uint2*>(pchild_.p), (uint32_t)n};
+    setRootKernel<<<1, 1, 0, st>>>(rootCid, static_cast<uint2*>(items_[0].p));
+    WB_TRY(hipGetLastError());
+    int it = 0;
+    int64_t items = 1;
+    uint32_t nodeBase = 1, primBase = 0;
+    int level = 0;
+    while (items > 0) {
+        if (++level > kMaxLevels) {
+            err = "wide BVH (device): deeper than the traversal stack";
+            return hipErrorUnknown;
+        }
+        const uint2* cur2 = static_cast<const uint2*>(items_[it].p);
+        uint4* cnt = static_cast<uint4*>(cnt_.p);
+        uint4* ofs = static_cast<uint4*>(ofs_.p);
+        wideCountKernel<<<blocks(items, tb), tb, 0, st>>>(T, cur2, (int)items, everyBlock, cnt);
+        WB_TRY(hipGetLastError());
+        WB_TRY(exclusiveScanU3(scanTemp_.p, cnt, ofs, (size_t)items, st));
+        wideWriteKernel<<<blocks(items, tb), tb, 0, st>>>(T, cur2, (int)items, cnt, ofs, nodeBase, primBase, slotCap, everyBlock,
+                                                          rootCid, prims, rank, nodes, reinterpret_cast<uint4*>(wprims),
+                                                          static_cast<uint2*>(items_[it ^ 1].p), misc);
+        WB_TRY(hipGetLastError());
+        uint32_t tot[4] = {0, 0, 0, 0};
+        WB_TRY(hipMemcpyAsync(tot, misc + kMiscTotA, 16, hipMemcpyDeviceToHost, st));
+        WB_TRY(hipStreamSynchronize(st));
+        if (tot[3]) {   // kMiscErr follows the totals
+            err = "wide BVH (device): encoding limits exceeded";
+            return hipErrorUnknown;
+        }
+        nodeBase += tot[0];
+        primBase += tot[1];
+        items = tot[2];
+        it ^= 1;
+    }
+    if ((int64_t)primBase != n) {
+        err = "wide BVH (device): primitive count mismatch";
+        return hipErrorUnknown;
+    }
+    depth = level;
+    slots = nodeBase;
+    return hipSuccess;
+}
+
+// The top level of an instanced scene (pt_device.hip rebuildInstancedTop): the same SAH stage over
+// the entries' boxes with one entry per leaf, the same collapse with a child block for every node,
+// no reference ranks (`rank` is the caller's, e.g. the identity).
+hipError_t WideDevBuilder::reserveTop(int64_t n) {
+    if (n <= 0) return hipSuccess;
+    WB_TRY(reserveScratch(n));
+    return reserveSah(n);
+}
+hipError_t WideDevBuilder::buildTop(const float* leafBoxes, int64_t n, const float4* prims, const uint32_t* rank,
+                                    uint32_t* nodes, uint32_t* wprims, uint32_t slotCap, hipStream_t st, std::string& err,
+                                    int& depth, int64_t& slots) {
+    depth = 0;
+    slots = 0;
+    if (n <= 0 || n >= ((int64_t)1 << 26)) {
+        err = "instanced BVH (device): entry count out of range";
+        return hipErrorInvalidValue;
+    }
+    WB_TRY(reserveScratch(n));
+    WB_TRY(hipMemsetAsync(misc_.p, 0, kMiscWords * 4, st));
+    WideDevIn in{};
+    in.leafBoxes = leafBoxes;
+    in.n = n;
+    const char* tv = std::getenv("PT_WIDE_TRAV_COST");
+    const float trav = tv && std::atof(tv) > 0.0 ? (float)std::atof(tv) : 1.0f;
+    WB_TRY(buildSah(in, st, trav, 1, err));
+    return collapseLevels(n, static_cast<const uint32_t*>(cid_[0].p), slotCap, 1u, prims, rank, nodes, wprims, st, err, depth,
+                          slots);
+}
+
+hipError_t WideDevBuilder::build(const WideDevIn& in, WideDevOut& out, hipStream_t st, std::string& err) {
+    const int64_t n = in.n;
+    out.depth = 0;
+    out.slots = 0;
+    if (n <= 0) return hipSuccess;
+    if (n >= ((int64_t)1 << 26)) {
+        err = "wide BVH (device): more than 2^26 primitives";
+        return hipErrorInvalidValue;
+    }
+    WB_TRY(reserveScratch(n));
     uint32_t* misc = static_cast<uint32_t*>(misc_.p);
     float4* pbox = static_cast<float4*>(pbox_.p);
     uint2* pchild = static_cast<uint2*>(pchild_.p);
@@ -1432,7 +1526,7 @@ hipError_t WideDevBuilder::build(const WideDevIn& in, WideDevOut& out, hipStream
     WB_TRY(hipMemsetAsync(misc, 0, kMiscWords * 4, st));
     int cur = 0;
     if (!ploc) {
-        WB_TRY(buildSah(in, st, trav, err));
+        WB_TRY(buildSah(in, st, trav, kMaxGroup, err));
     } else {
         plocInitKernel<<<blocks(n, tb), tb, 0, st>>>(in.leafBoxes, (int)n, pbox, static_cast<uint32_t*>(cid_[0].p));
         WB_TRY(hipGetLastError());
@@ -1489,48 +1583,8 @@ hipError_t WideDevBuilder::build(const WideDevIn& in, WideDevOut& out, hipStream
     const uint32_t* rootCid = static_cast<const uint32_t*>(cid_[cur].p);
 
     // 3. collapse + quantisation, level by level
-    const Tree T{pbox, pchild, (uint32_t)n};
-    const uint32_t slotCap = wideDevSlotCap(n);   // <= 2^24: child bases fit the kernels' 24-bit field
-    setRootKernel<<<1, 1, 0, st>>>(rootCid, static_cast<uint2*>(items_[0].p));
-    WB_TRY(hipGetLastError());
-    int it = 0;
-    int64_t items = 1;
-    uint32_t nodeBase = 1, primBase = 0;
-    int level = 0;
-    while (items > 0) {
-        if (++level > kMaxLevels) {
-            err = "wide BVH (device): deeper than the traversal stack";
-            return hipErrorUnknown;
-        }
-        const uint2* cur2 = static_cast<const uint2*>(items_[it].p);
-        uint4* cnt = static_cast<uint4*>(cnt_.p);
-        uint4* ofs = static_cast<uint4*>(ofs_.p);
-        wideCountKernel<<<blocks(items, tb), tb, 0, st>>>(T, cur2, (int)items, cnt);
-        WB_TRY(hipGetLastError());
-        WB_TRY(exclusiveScanU3(scanTemp_.p, cnt, ofs, (size_t)items, st));
-        wideWriteKernel<<<blocks(items, tb), tb, 0, st>>>(T, cur2, (int)items, cnt, ofs, nodeBase, primBase, slotCap, rootCid,
-                                                          in.prims, out.rank, out.nodes, reinterpret_cast<uint4*>(out.wprims),
-                                                          static_cast<uint2*>(items_[it ^ 1].p), misc);
-        WB_TRY(hipGetLastError());
-        uint32_t tot[4] = {0, 0, 0, 0};
-        WB_TRY(hipMemcpyAsync(tot, misc + kMiscTotA, 16, hipMemcpyDeviceToHost, st));
-        WB_TRY(hipStreamSynchronize(st));
-        if (tot[3]) {   // kMiscErr follows the totals
-            err = "wide BVH (device): encoding limits exceeded";
-            return hipErrorUnknown;
-        }
-        nodeBase += tot[0];
-        primBase += tot[1];
-        items = tot[2];
-        it ^= 1;
-    }
-    if ((int64_t)primBase != n) {
-        err = "wide BVH (device): primitive count mismatch";
-        return hipErrorUnknown;
-    }
-    out.depth = level;
-    out.slots = nodeBase;
-    return hipSuccess;
+    return collapseLevels(n, rootCid, wideDevSlotCap(n) /* <= 2^24: child bases fit the kernels' 24-bit field */, 0u, in.prims,
+                          out.rank, out.nodes, out.wprims, st, err, out.depth, out.slots);
 }
 
 }  // namespace pt

@@ -58,6 +58,15 @@ public:
     // Enqueues the build on `stream`; synchronises with it once per PLOC pass and per wide level
     // (the next launch's size).  Scratch is kept between builds of up to the same n.
     hipError_t build(const WideDevIn& in, WideDevOut& out, hipStream_t stream, std::string& err);
+    // The top level of an instanced scene over n entries (boxes: n x {min xyz, max xyz} on the
+    // device): the SAH stage with one entry per leaf and the collapse with a child block for every
+    // node (1 + 8 * wide nodes slots, at most slotCap), no reference ranks.  prims / rank: n x 3
+    // float4 entry records and n ranks, copied to wprims in leaf order ({.., rank}{.., entry}{..});
+    // the caller turns the leaf children into instance records.  reserveTop: the scratch of a
+    // build of n entries, so that the builds themselves allocate nothing once one has run.
+    hipError_t reserveTop(int64_t n);
+    hipError_t buildTop(const float* leafBoxes, int64_t n, const float4* prims, const uint32_t* rank, uint32_t* nodes,
+                        uint32_t* wprims, uint32_t slotCap, hipStream_t stream, std::string& err, int& depth, int64_t& slots);
 
 private:
     struct Buf {
@@ -66,7 +75,12 @@ private:
     };
     hipError_t reserve(Buf& b, size_t bytes);
     // step 2 by SAH (the root's id left in cid_[0][0])
-    hipError_t buildSah(const WideDevIn& in, hipStream_t stream, float trav, std::string& err);
+    hipError_t buildSah(const WideDevIn& in, hipStream_t stream, float trav, int maxGroup, std::string& err);
+    hipError_t reserveScratch(int64_t n);
+    hipError_t reserveSah(int64_t n);
+    hipError_t collapseLevels(int64_t n, const uint32_t* rootCid, uint32_t slotCap, uint32_t everyBlock, const float4* prims,
+                              const uint32_t* rank, uint32_t* nodes, uint32_t* wprims, hipStream_t stream, std::string& err,
+                              int& depth, int64_t& slots);
     Buf pbox_, pchild_, cid_[2], nn_, flag_, pos_, items_[2], cnt_, ofs_, scanTemp_, misc_;
     Buf sahCen_, sahRef_[2], sahLarge_[2], sahSmall_, sahSplit_, sahBins_, sahMulti_, sahBlk_, sahBlkR_, sahBlkO_, sahCnt_;
 };

@@ -91,6 +91,7 @@ EXPORTS = [
     "pt_scene_update_objects", "pt_trace_closest_ex", "pt_scene_wide_info", "pt_trace_closest_device",
     "pt_scene_build_bvh_ex", "pt_film_stats", "pt_preset_instanced", "pt_instanced_desc_free",
     "pt_scene_create_instanced", "pt_trace_occluded", "pt_trace_occluded_device",
+    "pt_scene_update_instances",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -129,6 +130,7 @@ _sig = {
     "pt_film_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "pt_scene_build_time": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "pt_scene_update_objects": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
+    "pt_scene_update_instances": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
     "pt_scene_bvh_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pt_scene_download_bvh": (C.c_int, [_P, _P]),
     "pt_scene_wide_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double),
@@ -344,6 +346,17 @@ class Scene:
         self.objects = self.objects.copy()
         self.objects[first:first + len(objs)] = objs
 
+    def update_instances(self, instances: np.ndarray, first: int = 0) -> None:
+        """pt_scene_update_instances: overwrite the transforms of instances [first, first +
+        len(instances)) (INSTANCE_DTYPE, `mesh` unchanged); the hierarchy must be rebuilt (build_bvh)
+        before the next render or trace.  From the second build on only the top level is rebuilt
+        (wide_info source 4)."""
+        inst = np.ascontiguousarray(instances, INSTANCE_DTYPE)
+        _check(lib.pt_scene_update_instances(self.h, _ptr(inst) if len(inst) else None, first, len(inst)),
+               "pt_scene_update_instances")
+        self.instances = self.instances.copy()
+        self.instances[first:first + len(inst)] = inst
+
     @property
     def build_ms(self) -> float:
         """Device time of the last LBVH build (HIP events)."""
@@ -357,7 +370,8 @@ class Scene:
         return {"depth": d.value, "nodes": n.value, "device_bytes": b.value}
 
     def wide_info(self) -> dict:
-        """The wide kernel's tree: depth, node slots, build ms, source (0 none yet, 1 host SAH, 2 device)."""
+        """The wide kernel's tree: depth, node slots, build ms, source (0 none yet, 1 host SAH, 2 device,
+        3 an instanced scene's full host build, 4 its top level rebuilt alone after update_instances)."""
         d, n, ms, src = C.c_int(), C.c_int64(), C.c_double(), C.c_int()
         _check(lib.pt_scene_wide_info(self.h, C.byref(d), C.byref(n), C.byref(ms), C.byref(src)), "pt_scene_wide_info")
         return {"depth": d.value, "slots": n.value, "build_ms": ms.value, "source": src.value}

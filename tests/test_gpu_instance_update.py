@@ -1,0 +1,358 @@
+"""pt_scene_update_instances: moving the instances of an instanced scene and rebuilding only what
+depends on the matrices (pt_scene_wide_info source 4).
+
+Why every check here is exact: a closest hit in an instanced scene is decided by (t, instance,
+primitive), and t is computed in object space from the instance's world-to-object rows; the
+top-level tree (built on the device after an update, on the host in a fresh scene) and the mesh
+trees' plane quantum decide only which nodes are visited.  The rows of a rebuilt scene come from
+the code a fresh scene's build runs, and so do the scene scalars, so a scene rebuilt after an
+update returns bit for bit the hit records -- and therefore the frames -- of a fresh
+Scene.instanced of the same matrices.  A mismatch is a bug, not rounding.
+"""
+import numpy as np
+import pytest
+import torch  # noqa: F401  before libpt.so loads (the two must share torch's HIP runtime)
+
+from helpers import OBJECT_DTYPE, random_rays, random_soup, rays_to_struct
+
+pytestmark = pytest.mark.gpu
+
+
+def random_transforms(n, seed, reach=30.0):
+    """Rotations with uniform scales in [0.5, 2] and translations in +-reach."""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((n, 12), np.float32)
+    for i in range(n):
+        q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+        s = rng.uniform(0.5, 2.0)
+        out[i] = np.concatenate([q * s, rng.uniform(-reach, reach, (3, 1))], 1).reshape(-1)
+    return out
+
+
+def flatten(objects, mesh_first, mesh_count, instances):
+    """World-space objects of an instanced description (float64 transform, rounded once): ray targets."""
+    parts = []
+    for inst in instances:
+        m = inst["m"].astype(np.float64).reshape(3, 4)
+        f, c = int(mesh_first[inst["mesh"]]), int(mesh_count[inst["mesh"]])
+        o = objects[f:f + c].copy()
+        v = o["v"].astype(np.float64)
+        out = (v.reshape(-1, 3, 3) @ m[:, :3].T + m[:, 3]).reshape(-1, 9)
+        sph = o["type"] == 1
+        if sph.any():
+            out[sph, :3] = v[sph, :3] @ m[:, :3].T + m[:, 3]
+            out[sph, 3] = v[sph, 3] * np.cbrt(abs(np.linalg.det(m[:, :3])))
+            out[sph, 4:] = 0
+        o["v"] = out.astype(np.float32)
+        parts.append(o)
+    return np.concatenate(parts) if parts else np.zeros(0, OBJECT_DTYPE)
+
+
+def camera_rays(pt, cam, w, h, seed=0):
+    rng = np.random.default_rng(seed)
+    c = pt.camera_to_array(cam)
+    org, ll, hor, ver = c[0:3], c[3:6], c[6:9], c[9:12]
+    ys, xs = np.mgrid[0:h, 0:w]
+    u = ((xs + rng.random(xs.shape)) / w).reshape(-1, 1)
+    v = ((ys + rng.random(ys.shape)) / h).reshape(-1, 1)
+    rays = np.zeros((w * h, 6), np.float32)
+    rays[:, :3] = org
+    rays[:, 3:] = ll + u * hor + v * ver - org
+    return rays
+
+
+def assert_same_hits(got, want, min_hits=1):
+    for f in ("hit", "obj", "mat", "front_face"):
+        np.testing.assert_array_equal(got[f], want[f], err_msg=f)
+    h = want["hit"] == 1
+    assert h.sum() >= min_hits, h.sum()
+    for f in ("t", "p", "n"):
+        np.testing.assert_array_equal(got[f][h].view(np.uint32), want[f][h].view(np.uint32), err_msg=f)
+
+
+class World:
+    """Meshes (object ranges) and a way to make scenes and rays of them."""
+
+    def __init__(self, pt, gpu, meshes, mats):
+        self.pt, self.gpu, self.mats = pt, gpu, mats
+        self.objs = np.concatenate(meshes) if sum(len(m) for m in meshes) else np.zeros(0, OBJECT_DTYPE)
+        self.count = np.array([len(m) for m in meshes], np.int64)
+        self.first = np.concatenate([[0], np.cumsum(self.count)[:-1]]).astype(np.int64)
+
+    def instances(self, m, mesh):
+        inst = np.zeros(len(m), self.pt.INSTANCE_DTYPE)
+        inst["m"] = m
+        inst["mesh"] = mesh
+        return inst
+
+    def scene(self, inst):
+        return self.pt.Scene.instanced(self.objs, self.first, self.count, inst, self.mats, device=self.gpu)
+
+    def rays(self, inst, n, seed, radius=60.0):
+        flat = flatten(self.objs, self.first, self.count, inst)
+        return rays_to_struct(random_rays(n, seed=seed, radius=radius, objects=flat), self.pt.RAY_DTYPE)
+
+    def check(self, scene, inst, n_rays, seed, radius=60.0, occluded=False, min_hits=100):
+        """`scene` (rebuilt) against a fresh scene of `inst`."""
+        pt = self.pt
+        fresh = self.scene(inst)
+        assert fresh.wide_info()["source"] == 3
+        np.testing.assert_array_equal(scene.instances, inst)
+        rays = self.rays(inst, n_rays, seed, radius)
+        got, _ = scene.trace(rays, kernel=pt.KERNEL_WIDE)
+        want, _ = fresh.trace(rays, kernel=pt.KERNEL_WIDE)
+        assert_same_hits(got, want, min_hits)
+        if occluded:
+            og, _ = scene.occluded(rays)
+            ow, _ = fresh.occluded(rays)
+            np.testing.assert_array_equal(og, ow)
+            np.testing.assert_array_equal(og, want["hit"].astype(np.uint8))
+
+
+@pytest.fixture(scope="module")
+def two_soups(pt, gpu):
+    a, mats = random_soup(600, 60, seed=21, spread=4.0)
+    b, _ = random_soup(300, 30, seed=22, spread=3.0)
+    return World(pt, gpu, [a, b], mats)
+
+
+def forty(world, seed):
+    return world.instances(random_transforms(40, seed), np.arange(40) % 2)
+
+
+def test_update_equals_fresh_scene(pt, two_soups):
+    w = two_soups
+    s = w.scene(forty(w, 23))
+    assert s.wide_info()["source"] == 3
+    second = forty(w, 25)
+    s.update_instances(second)
+    rays = w.rays(second, 64, seed=24)
+    with pytest.raises(pt.PtError):   # stale until the build
+        s.trace(rays, kernel=pt.KERNEL_WIDE)
+    with pytest.raises(pt.PtError):
+        s.occluded(rays)
+    s.build_bvh()    # (may be the full build, laid out for updates)
+    s.build_bvh()
+    assert s.wide_info()["source"] == 4
+    assert s.build_ms > 0.0
+    w.check(s, second, 16384, seed=24, occluded=True, min_hits=1000)
+
+
+@pytest.mark.parametrize("count", [1, 2, 9, 65, 600])
+def test_tree_shapes(pt, gpu, two_soups, count):
+    """A single entry, one partly filled node, the first second level, more entries than a wave, a
+    multi-level top; a mesh that enters at its root (two triangles: its root has leaf children),
+    a re-braided one (several entries per instance) and an instance of an empty mesh."""
+    tri = np.zeros(2, OBJECT_DTYPE)
+    tri["type"] = 3
+    tri["v"][0] = [-2, -2, 0, 2, -2, 0, 2, 2, 0.5]
+    tri["v"][1] = [-2, -2, 0, 2, 2, 0.5, -2, 2, 0]
+    soup = two_soups.objs[:int(two_soups.count[0])]
+    w = World(pt, gpu, [tri, soup, np.zeros(0, OBJECT_DTYPE)], two_soups.mats)
+    reach = 30.0 * np.cbrt(count / 40.0)
+    mesh = np.insert(np.arange(count) % 2, count // 2, 2)   # the empty mesh among the others
+
+    def inst(seed):
+        return w.instances(random_transforms(count + 1, seed, reach), mesh)
+
+    s = w.scene(inst(31))
+    second = inst(32)
+    s.update_instances(second)
+    s.build_bvh()
+    s.build_bvh()
+    assert s.wide_info()["source"] == 4
+    w.check(s, second, 4096, seed=33, radius=2.0 * reach, occluded=True, min_hits=20)
+
+
+def test_transform_classes(pt, two_soups):
+    w = two_soups
+    inst = forty(w, 23)
+    s = w.scene(inst)
+    s.update_instances(inst)
+    s.build_bvh()   # laid out for updates: the builds below are the fast ones
+    steps = [(0, [1, 0, 0, 5.5, 0, 1, 0, -7.25, 0, 0, 1, 3.0]),       # general -> translation only
+             (1, [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]),               # general -> identity
+             (0, list(random_transforms(1, 41)[0]))]                  # translation -> rotation
+    for k, (i, m) in enumerate(steps):
+        inst = inst.copy()
+        inst["m"][i] = m
+        s.update_instances(inst[i:i + 1], first=i)
+        s.build_bvh()
+        assert s.wide_info()["source"] == 4, k
+        w.check(s, inst, 4096, seed=42 + k)
+
+
+def test_partial_update_and_reuse(pt, two_soups):
+    w = two_soups
+    inst = forty(w, 23)
+    s = w.scene(inst)
+    moved = inst.copy()
+    moved["m"][3:5] = random_transforms(2, 51)
+    s.update_instances(moved[3:5], first=3)
+    np.testing.assert_array_equal(s.instances[:3], inst[:3])
+    np.testing.assert_array_equal(s.instances[5:], inst[5:])
+    s.build_bvh()
+    w.check(s, moved, 4096, seed=52)
+    rng = np.random.default_rng(53)
+    sizes = []
+    for frame in range(3):   # an animation: every instance drifts a little
+        moved = moved.copy()
+        moved["m"][:, [3, 7, 11]] += rng.uniform(-1.0, 1.0, (40, 3)).astype(np.float32)
+        s.update_instances(moved)
+        s.build_bvh()
+        assert s.wide_info()["source"] == 4, frame
+        sizes.append(s.bvh_info()["device_bytes"])
+        w.check(s, moved, 4096, seed=54 + frame)
+    assert sizes[0] == sizes[1] == sizes[2] > 0
+
+
+def test_reach_fallback(pt, gpu):
+    """Instances shrunk 100x where they stand (the 3 x 3 part of every matrix times 0.01): the world
+    keeps its size, so it reaches 100x farther into their object spaces than the mesh trees were
+    quantised for -- that build is the full one.
+
+    Triangle meshes only, for a reason that has nothing to do with the update: a sphere shrunk to a
+    radius of 0.006 and seen from 60 units away (r / distance = 1e-4) is beyond the reference's
+    sphere test, which solves its quadratic in float (cuda_object.h:44-68) -- the cancellation
+    error of b^2 - ac there is larger than r^2, so the test reports hits for rays that pass the
+    sphere at several radii, and which of those false hits are found depends on which boxes the
+    ray enters, i.e. on the planes' quantum.  A dynamic scene's mesh trees are quantised for twice
+    the reach, so with the two sphere-carrying soups of the other tests 1 ray of 16,384 differs
+    here (MI355X: ray 2060 of seed 61 'hits' a sphere of radius 0.0058 that it misses by the
+    float64 discriminant -2.46; 8,125 hits against the fresh scene's 8,124).  Triangles have no
+    such regime: their test's error stays far inside the planes' outward margin."""
+    a, mats = random_soup(600, 0, seed=21, spread=4.0)
+    b, _ = random_soup(300, 0, seed=22, spread=3.0)
+    w = World(pt, gpu, [a, b], mats)
+    inst = forty(w, 23)
+    s = w.scene(inst)
+    s.update_instances(inst)
+    s.build_bvh()
+    s.build_bvh()
+    assert s.wide_info()["source"] == 4
+    small = inst.copy()
+    small["m"][:, [0, 1, 2, 4, 5, 6, 8, 9, 10]] *= np.float32(0.01)
+    s.update_instances(small)
+    s.build_bvh()
+    assert s.wide_info()["source"] == 3
+    w.check(s, small, 16384, seed=61, min_hits=5)
+    nxt = small.copy()
+    nxt["m"][:, [3, 7, 11]] += np.float32(0.25)
+    s.update_instances(nxt)
+    s.build_bvh()
+    assert s.wide_info()["source"] == 4
+    w.check(s, nxt, 16384, seed=62, min_hits=5)
+
+
+def test_frame_after_update(pt, gpu):
+    ip = pt.InstancedPreset("bunny_cornell", 96, 96)
+    s = pt.Scene.instanced(ip.objects, ip.mesh_first, ip.mesh_count, ip.instances, ip.materials, device=gpu)
+    moved = ip.instances.copy()
+    for step in (0.5, 1.0):   # the bunny (instance 1) moves in two steps: the second build is the fast one
+        moved = ip.instances.copy()
+        moved["m"][1, [3, 7, 11]] += np.float32(step) * np.array([40.0, 15.0, -30.0], np.float32)
+        s.update_instances(moved[1:2], first=1)
+        s.build_bvh()
+    assert s.wide_info()["source"] == 4
+    fresh = pt.Scene.instanced(ip.objects, ip.mesh_first, ip.mesh_count, moved, ip.materials, device=gpu)
+    a, sa = pt.render(s, pt.Film(96, 96, 5, device=gpu), ip.camera, 4, 8, kernel=pt.KERNEL_WIDE, rng=pt.RNG_SAMPLE)
+    b, sb = pt.render(fresh, pt.Film(96, 96, 5, device=gpu), ip.camera, 4, 8, kernel=pt.KERNEL_WIDE, rng=pt.RNG_SAMPLE)
+    np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert sa.rays == sb.rays
+    still, _ = pt.render(pt.Scene.instanced(ip.objects, ip.mesh_first, ip.mesh_count, ip.instances, ip.materials,
+                                            device=gpu),
+                         pt.Film(96, 96, 5, device=gpu), ip.camera, 4, 8, kernel=pt.KERNEL_WIDE, rng=pt.RNG_SAMPLE)
+    assert not np.array_equal(a, still)   # (the move shows in the frame)
+    cam = pt.InstancedPreset("bunny_cornell", 32, 32).camera
+    a, sa = pt.render(s, pt.Film(32, 32, 5, device=gpu), cam, 2, 8, kernel=pt.KERNEL_WIDE, rng=pt.RNG_COMPAT)
+    b, sb = pt.render(fresh, pt.Film(32, 32, 5, device=gpu), cam, 2, 8, kernel=pt.KERNEL_WIDE, rng=pt.RNG_COMPAT)
+    np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert sa.rays == sb.rays
+
+
+def test_rules(pt, gpu, two_soups):
+    w = two_soups
+    inst = forty(w, 23)
+    s = w.scene(inst)
+    rays = w.rays(inst, 2048, seed=71)
+    before, _ = s.trace(rays, kernel=pt.KERNEL_WIDE)
+
+    def unchanged():
+        np.testing.assert_array_equal(s.instances, inst)
+        again, _ = s.trace(rays, kernel=pt.KERNEL_WIDE)   # still built, the same hits
+        assert_same_hits(again, before)
+
+    flat = pt.Scene(w.objs, w.mats, device=gpu)
+    with pytest.raises(pt.PtError):
+        flat.update_instances(inst[:1])
+    bad = inst.copy()
+    bad["mesh"][4] = 1 - bad["mesh"][4]
+    with pytest.raises(pt.PtError):
+        s.update_instances(bad)
+    unchanged()
+    with pytest.raises(pt.PtError):
+        s.update_instances(inst[:2], first=39)
+    with pytest.raises(pt.PtError):
+        s.update_instances(inst[:1], first=-1)
+    unchanged()
+    bad = inst.copy()
+    bad["m"][7, 5] = np.nan
+    with pytest.raises(pt.PtError):
+        s.update_instances(bad)
+    bad["m"][7, 5] = np.inf
+    with pytest.raises(pt.PtError):
+        s.update_instances(bad)
+    unchanged()
+    bad = inst.copy()
+    bad["m"][5, :] = 0.0
+    with pytest.raises(pt.PtError) as e:
+        s.update_instances(bad[3:8], first=3)   # (valid ones before it in the range: nothing is taken over)
+    assert "pt_scene_update_instances" in str(e.value) and "instance 5" in str(e.value) and "singular" in str(e.value)
+    unchanged()
+    s.update_instances(inst[:0])   # n == 0: nothing changes, nothing goes stale
+    unchanged()
+    with pytest.raises(pt.PtError):
+        s.update_objects(w.objs[:1])
+    unchanged()
+
+
+# Node visits of the rebuilt bunny field relative to a fresh host-built scene of the same matrices,
+# at most 1 + kVisitsMargin: the measured excess (0.00281, see the docstring below) plus 0.05 for the
+# SAH's sensitivity to box rounding.
+kVisitsMargin = 0.00281 + 0.05
+
+
+def test_tree_quality_bunny_field(pt, gpu):
+    """Every second bunny of the C5 field moved by up to half the grid spacing, rebuilt, against a
+    fresh host-built scene: the same hits, and node_visits within 1 + kVisitsMargin of the fresh
+    scene's.  Measured on an MI355X with this input: 222,391 node visits through the rebuilt
+    scene (top level built on the device, mesh trees quantised for twice the reach) against 221,767
+    through the fresh one (both levels built on the host), ratio 1.00281."""
+    ip = pt.InstancedPreset("bunny_field")
+    fp = pt.Preset("bunny_field")
+    t = ip.instances["m"][1:, [3, 7, 11]].astype(np.float64)
+    d = np.linalg.norm(t[1:] - t[0], axis=1)
+    spacing = float(d[d > 0].min())
+    rng = np.random.default_rng(81)
+    moved = ip.instances.copy()
+    k = np.arange(1, len(moved), 2)
+    moved["m"][k, 3] += rng.uniform(-0.5, 0.5, len(k)).astype(np.float32) * np.float32(spacing)
+    moved["m"][k, 11] += rng.uniform(-0.5, 0.5, len(k)).astype(np.float32) * np.float32(spacing)
+    s = pt.Scene.instanced(ip.objects, ip.mesh_first, ip.mesh_count, ip.instances, ip.materials, device=gpu)
+    s.update_instances(moved)
+    s.build_bvh()
+    s.build_bvh()
+    assert s.wide_info()["source"] == 4
+    fresh = pt.Scene.instanced(ip.objects, ip.mesh_first, ip.mesh_count, moved, ip.materials, device=gpu)
+    lo, hi = fp.objects["v"][:, :3].min(0), fp.objects["v"][:, :3].max(0)
+    rays = rays_to_struct(np.concatenate([
+        camera_rays(pt, fp.camera, 128, 128, seed=1),
+        random_rays(16384, seed=3, center=(lo + hi) / 2, radius=float(np.linalg.norm(hi - lo)) * 0.6,
+                    objects=fp.objects)]), pt.RAY_DTYPE)
+    got, sg = s.trace(rays, kernel=pt.KERNEL_WIDE)
+    want, sw = fresh.trace(rays, kernel=pt.KERNEL_WIDE)
+    assert_same_hits(got, want, 1000)
+    ratio = sg.node_visits / sw.node_visits
+    print(f"node_visits rebuilt {sg.node_visits} fresh {sw.node_visits} ratio {ratio:.5f}; "
+          f"build {s.build_ms:.3f} ms device, {s.wide_info()['build_ms']:.3f} ms wall")
+    assert ratio <= 1.0 + kVisitsMargin, ratio
