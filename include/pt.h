@@ -34,7 +34,19 @@ enum pt_status {
 
 /* Object and material types: simulation/cuda_object.h:12-14, simulation/material.h:13-15 */
 enum { PT_SPHERE = 1, PT_TRIANGLE = 3 };
-enum { PT_LAMBERTIAN = 1, PT_METAL = 2, PT_DIELECTRIC = 4 };
+enum { PT_LAMBERTIAN = 1, PT_METAL = 2, PT_DIELECTRIC = 4, PT_EMISSIVE = 8 };
+/* PT_EMISSIVE (no counterpart in the reference, whose only light is its sky): albedo[3] is the
+ * emitted radiance E (RGB), fuzz and ir are ignored.  A ray that hits an emissive object, from
+ * either side, ends its path there: the path contributes att * E per channel (att = the path's
+ * attenuation so far, (1,1,1) on a primary hit; one fp32 multiply per channel).  The hit draws no
+ * random number and counts in pt_stats.rays like any other.  A path that runs out of bounces still
+ * returns sky x attenuation.  Any other unknown material type absorbs (a black contribution).
+ * Every component of E must be finite and in [0, PT_MAX_RADIANCE] (pt_scene_create checks it);
+ * the same bound holds for the sky colours of pt_scene_set_sky.  The bound comes from the
+ * sample-mode accumulator, signed 32.32 fixed point: a pixel's sum of N samples of radiance <= R
+ * is exact while N * R < 2^31, so 1024 keeps 2^21 accumulated samples per pixel safe (next to the
+ * "at most 2^24 - 1 accumulated samples" of PT_RENDER_ACCUMULATE, which holds for radiance <= 128). */
+#define PT_MAX_RADIANCE 1024.0f
 
 /* One scene object, the reference's CudaObj (cuda_object.h:16-123) without device pointers.
  * sphere: v[0..2] = centre, v[3] = radius (negative radius = hollow sphere, as in RTIOW)
@@ -110,13 +122,22 @@ int pt_camera_move(pt_camera* cam, int dir, float delta_time);
  * "random_world" (main.cu:198-256), "test_world" (main.cu:57-117), "rtiow" (C1),
  * "cornell" (C2), "bunny_cornell" (C3), "bunny_field" (C5), "bunny_field_x4" (C5 at 4x the
  * triangles: 840 half-size bunnies, an HBM-resident stress case).  models_dir holds
- * cornellbox/<part>.obj and bunny/bunny.obj.  width/height <= 0 keep the preset's frame. */
+ * cornellbox/<part>.obj and bunny/bunny.obj.  width/height <= 0 keep the preset's frame.
+ * "cornell_lit" / "bunny_cornell_lit": "cornell" / "bunny_cornell" bit for bit (objects, camera, frame)
+ * except that the lamp's triangles (light.obj) use a PT_EMISSIVE material of radiance (17, 12, 4),
+ * appended after the box's three materials; they are meant for a black sky (pt_preset_sky). */
 int pt_preset_scene(const char* name, const char* models_dir, int width, int height, pt_scene_desc* out);
+/* The sky a preset is meant to be rendered under (pt_scene_set_sky's arguments): black for the
+ * "_lit" presets, the reference's gradient (1,1,1) -> (0.5,0.7,1) for every other known name,
+ * PT_ERR_INVALID for an unknown one.  (A call of its own: the descriptor structs are allocated by
+ * the caller and keep their size under ABI version 1.) */
+int pt_preset_sky(const char* name, float horizon[3], float zenith[3]);
 void pt_scene_desc_free(pt_scene_desc* desc);
 /* The instanced form of a preset: "bunny_field" (C5: the Cornell box once and the bunny mesh,
  * scaled x250 in object space, placed 210 times by translations -- the same grid, order and frame
  * as pt_preset_scene's flattened 1,043,312 triangles), "bunny_cornell" (box + one bunny), "cornell"
- * (the box alone).  The box is instance 0 with the identity transform. */
+ * (the box alone), and the "_lit" forms of the last two (pt_preset_scene).  The box is instance 0
+ * with the identity transform. */
 int pt_preset_instanced(const char* name, const char* models_dir, int width, int height, pt_instanced_desc* out);
 void pt_instanced_desc_free(pt_instanced_desc* desc);
 /* OBJ mesh -> triangle objects (objl::Loader::LoadFile, OBJ_Loader.hpp:426-708, flattened to
@@ -141,6 +162,15 @@ int pt_write_png_rgba8(const char* path, const uint8_t* rgba, int width, int hei
  * copyObjMatsToDevice, one copyTrianglesToDevice<<<1,1>>> per triangle). */
 int pt_scene_create(int device, const pt_object* objs, int64_t n_objects,
                     const pt_material* mats, int64_t n_materials, pt_scene** out);
+/* The scene's sky: a ray that leaves the scene returns ((1 - t) * horizon + t * zenith) * attenuation
+ * with t = 0.5 * (unit direction's y + 1), in the reference's operation order (main.cu:34-36).  A new
+ * scene, flat or instanced, has the reference's sky, horizon (1,1,1) and zenith (0.5,0.7,1), and
+ * renders exactly as it did before this call existed; setting those values gives the same bits.
+ * The hierarchy is not touched (no rebuild).  The colours travel by value with each render's launch:
+ * the call takes effect for renders enqueued after it, and a frame in flight keeps the sky it was
+ * enqueued with.  PT_ERR_INVALID, and the sky left as it was, for a NULL argument or a component
+ * that is not finite, negative or above PT_MAX_RADIANCE. */
+int pt_scene_set_sky(pt_scene* scene, const float horizon[3], const float zenith[3]);
 /* Replaces lbvh::buildBVH (bvh.h:132-145), entirely on the device: scene box, Morton codes
  * (morton_code.h:19-45), a stable radix sort by code (the reference's host std::stable_sort,
  * morton_code.h:64-75), leaf records, Karras hierarchy (bvh.h:17-115), bottom-up refit with
@@ -304,7 +334,8 @@ int pt_render(pt_scene* scene, pt_film* film, const pt_camera* cam, int spp, int
  *   main.cu:307-340, 489-528) and outputs sqrt(all accumulated samples' sum / their count);
  *   compat mode continues the film's XORWOW streams, sample mode continues the sample index.
  *   pt_film_clear() restarts the accumulation (e.g. after pt_camera_move).  At most 2^24 - 1
- *   accumulated samples per pixel.
+ *   accumulated samples per pixel.  (Sample mode's 32.32 fixed-point sums are exact while
+ *   samples x radiance < 2^31: with emitters or a sky at PT_MAX_RADIANCE = 1024, 2^21 samples.)
  * out_format: PT_OUT_RGB32F (3 floats per pixel), PT_OUT_RGBA8 (4 bytes per pixel, quantised on
  *   the device exactly like PngImage::saveColor, png_image.h:24-30: (uint8)(clamp(c,0,0.999)*256),
  *   alpha 255; rows in film order, row 0 = bottom, pt_write_png_rgba8 flips them) or

@@ -901,6 +901,21 @@ __device__ __forceinline__ float3 sky(float3 d, float3 att) {
     float3 c = add(scale(1.0f - t, f3(1.0f, 1.0f, 1.0f)), scale(t, f3(0.5f, 0.7f, 1.0f)));
     return mul(c, att);
 }
+// The same between a scene's own horizon H and zenith Z colours (pt_scene_set_sky; wave-uniform,
+// from the kernel arguments), in the same operation order: H = (1, 1, 1), Z = (0.5, 0.7, 1) give the
+// bits of the function above.
+__device__ __forceinline__ float3 sky(float3 d, float3 att, float3 H, float3 Z) {
+    float3 ud = normalize3(d);
+    float t = 0.5f * (ud.y + 1.0f);
+    float3 c = add(scale(1.0f - t, H), scale(t, Z));
+    return mul(c, att);
+}
+// An emissive surface (PT_EMISSIVE: radiance E in the albedo slot of the shading record) ends the
+// path with att * E; no draw.  Beside the absorb exit of scatter / scatterInto, which every
+// material type other than 1, 2 and 4 takes.
+__device__ __forceinline__ float3 emitted(const HitRec& h, float3 att) {
+    return h.type == PT_EMISSIVE ? mul(att, xyz(h.m0)) : f3(0.0f, 0.0f, 0.0f);
+}
 
 // ------------------------------------------------------------------------ kernels
 struct RenderParams {
@@ -953,7 +968,17 @@ struct RenderParams {
     const uint32_t* critList;
     const uint8_t* critFlag;
     uint32_t* pixRays;
+    // Lit scenes (`lit`: an emissive material or a sky other than the reference's; the kernels' LIT
+    // instantiations -- every other scene runs the kernels without either, as before): the scene's
+    // sky at enqueue time (pt_scene_set_sky), by value.
+    float3 skyH, skyZ;
+    int lit;
 };
+template <bool LIT>
+__device__ __forceinline__ float3 skyOf(const RenderParams& P, float3 d, float3 att) {
+    if constexpr (LIT) return sky(d, att, P.skyH, P.skyZ);
+    else return sky(d, att);
+}
 
 // compat critical pixels: how many (PT_CRIT_PIXELS) and how many per wave (PT_CRIT_LANES)
 #ifndef PT_CRIT_PIXELS
@@ -1052,7 +1077,7 @@ __device__ __forceinline__ void lensOffset(float3 right, float3 up, float lens, 
     d = sub(d, off);
 }
 
-template <int STACK, bool SAMPLE>
+template <int STACK, bool SAMPLE, bool LIT = false>
 __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
     __shared__ uint32_t stk[STACK * kWave];
     const int lane = threadIdx.x;
@@ -1100,7 +1125,7 @@ __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
             }
         };
         if (P.max_depth <= 0) {
-            while (sample < P.spp) { newPath(); sum = add(sum, sky(d, att)); sample++; flush(); }
+            while (sample < P.spp) { newPath(); sum = add(sum, skyOf<LIT>(P, d, att)); sample++; flush(); }
         } else if (P.spp > 0) {
             newPath();
             uint32_t* my = stk + lane;
@@ -1113,18 +1138,18 @@ __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
                 bool done = false;
                 float3 contrib;
                 if (k < 0) {
-                    contrib = sky(d, att);
+                    contrib = skyOf<LIT>(P, d, att);
                     done = true;
                 } else {
                     HitRec h = makeHit(P.S, k, closest, o, d);
                     float3 na;
                     if (!scatter(P.S, h, d, na, g)) {
-                        contrib = f3(0.0f, 0.0f, 0.0f);
+                        contrib = LIT ? emitted(h, att) : f3(0.0f, 0.0f, 0.0f);
                         done = true;
                     } else {
                         att = mul(att, na);
                         o = h.p;
-                        if (depthLeft == 0) { contrib = sky(d, att); done = true; }
+                        if (depthLeft == 0) { contrib = skyOf<LIT>(P, d, att); done = true; }
                     }
                 }
                 if (done) {
@@ -1249,12 +1274,19 @@ __device__ __forceinline__ DevScene ldScene(KArgs k) {
     return S;
 }
 
+template <bool LIT>
+__device__ __forceinline__ float3 skyK(float3 d, float3 att) {
+    if constexpr (LIT) return sky(d, att, ld3(kargs()->skyH), ld3(kargs()->skyZ));
+    else return sky(d, att);
+}
+
 // INST (with WIDE): an instanced scene's two-level tree (pt_scene_create_instanced): a NODE step
 // that reaches an instance record moves the lane's ray into the instance's object space and its
 // bottom-level tree, a stack marker brings it back; no speculative traversal (a parked primitive
 // group would belong to another space), no reference-order redo (instanced frames are held to a
 // tolerance, not bit for bit).
-template <int STACK, bool SAMPLE, bool WIDE, bool INST = false>
+// LIT: scenes with an emissive material or a sky of their own (RenderParams::lit).
+template <int STACK, bool SAMPLE, bool WIDE, bool INST = false, bool LIT = false>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPerEU<STACK, SAMPLE, WIDE>))) void renderKernelWF(RenderParams P) {
     // Deep trees (binary kernels) keep 32 stack entries per lane in LDS (8 KB per wave: 5 waves
     // per SIMD) and the rare deeper entries in global memory (stackSpill, per wave slot and lane).
@@ -1554,6 +1586,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         depthLeft = Q_.max_depth;                                                                  \
     } while (0)
 
+    // The sky colour of (d, att); LIT: the scene's horizon and zenith from the kernel arguments (six
+    // scalar loads where a path ends, not six registers held across the step loop).
+#define PT_SKY() skyK<LIT>(d, att)
+
     bool started = false;
     if constexpr (SAMPLE) {
         // Every lane starts with needTask: the first loop iteration is a SHADE step that hands
@@ -1570,7 +1606,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                     while (ts.y < ts.z) {
                         taskState[lane].y = ts.y;
                         PT_NEW_PATH();
-                        sum = add(sum, sky(d, att));
+                        sum = add(sum, PT_SKY());
                         ts.y++;
                         if (ts.y < ts.z) (void)kargs();   // (see the SHADE step's note on this read)
                     }
@@ -1584,7 +1620,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         if (P.max_depth <= 0) {
             for (; sample < nSamples; sample++) {
                 PT_NEW_PATH();
-                sum = add(sum, sky(d, att));
+                sum = add(sum, PT_SKY());
             }
         } else if (nSamples > 0) {
             PT_NEW_PATH();
@@ -1919,7 +1955,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 bool done = false;
                 float3 contrib = f3(0.0f, 0.0f, 0.0f);
                 if (best < 0) {
-                    contrib = sky(d, att);
+                    contrib = PT_SKY();
                     done = true;
                 } else {
                     int objI_;
@@ -1927,10 +1963,11 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                                     : (WIDE ? makeHitFrom(kargs()->S.wshade, best & (int)kPrimMask, closest, o, d)
                                             : makeHit(S, best, closest, o, d));
                     if (!scatterInto(h, d, att, g)) {
+                        if constexpr (LIT) contrib = emitted(h, att);
                         done = true;
                     } else {
                         o = h.p;
-                        if (depthLeft == 0) { contrib = sky(d, att); done = true; }
+                        if (depthLeft == 0) { contrib = PT_SKY(); done = true; }
                     }
                 }
                 if (done) {
@@ -2046,6 +2083,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #undef PT_BEGIN_RAY
 #undef PT_CRIT_TRACE
 #undef PT_NEW_PATH
+#undef PT_SKY
 #undef PT_TAKE_TASKS
 #undef PT_FINISH_TASK
 #undef PT_DIAG_ADD
@@ -2063,9 +2101,15 @@ int launchCompatWide(int stack, const void* params, hipStream_t st) {
     const RenderParams& P = *static_cast<const RenderParams*>(params);
     const int grid = P.compatGrid;
     switch (stack) {
-        case 8: renderKernelWF<8, false, true><<<grid, kWave, 0, st>>>(P); break;
-        case 16: renderKernelWF<16, false, true><<<grid, kWave, 0, st>>>(P); break;
-        case 24: renderKernelWF<24, false, true><<<grid, kWave, 0, st>>>(P); break;
+#define PT_COMPAT_WIDE(S)                                                                    \
+        case S:                                                                                  \
+            if (P.lit) renderKernelWF<S, false, true, false, true><<<grid, kWave, 0, st>>>(P);   \
+            else renderKernelWF<S, false, true><<<grid, kWave, 0, st>>>(P);                      \
+            break;
+        PT_COMPAT_WIDE(8)
+        PT_COMPAT_WIDE(16)
+        PT_COMPAT_WIDE(24)
+#undef PT_COMPAT_WIDE
         default: return -1;
     }
     return 0;
@@ -3143,6 +3187,8 @@ struct pt_scene {
     size_t deviceBytes = 0;
     double buildMs = 0.0;                   // last pt_scene_build_bvh, device time (HIP events)
     float sceneCE[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // tight scene box: centre, largest extent (DevScene)
+    float skyH[3] = {1.0f, 1.0f, 1.0f}, skyZ[3] = {0.5f, 0.7f, 1.0f};   // pt_scene_set_sky (default: main.cu:34-36)
+    bool hasEmissive = false;               // any PT_EMISSIVE material
     float mixLim = -1.0f;                          // DevScene::mixLim (-1: every ray takes the reference order)
     // instanced scenes (pt_scene_create_instanced): meshes = object ranges of `objs`, instances
     bool instanced = false;
@@ -3881,24 +3927,25 @@ int setDevice(int dev) {
     return PT_OK;
 }
 
-template <int S>
+// LIT = P.lit (dispatchRender): the kernels with the emissive exit and the scene's own sky
+template <int S, bool LIT>
 void launchRenderWide(const RenderParams& P, hipStream_t st) {
     if (P.S.winst) {   // an instanced scene's two-level tree
-        if (P.pixAcc) renderKernelWF<S, true, true, true><<<P.nwaves, kWave, 0, st>>>(P);
-        else renderKernelWF<S, false, true, true><<<P.compatGrid, kWave, 0, st>>>(P);
+        if (P.pixAcc) renderKernelWF<S, true, true, true, LIT><<<P.nwaves, kWave, 0, st>>>(P);
+        else renderKernelWF<S, false, true, true, LIT><<<P.compatGrid, kWave, 0, st>>>(P);
         return;
     }
-    if (P.pixAcc) renderKernelWF<S, true, true><<<P.nwaves, kWave, 0, st>>>(P);
-    else pt::launchCompatWide(S, &P, st);   // (its own translation unit, pt_compat.hip)
+    if (P.pixAcc) renderKernelWF<S, true, true, false, LIT><<<P.nwaves, kWave, 0, st>>>(P);
+    else pt::launchCompatWide(S, &P, st);   // (its own translation unit, pt_compat.hip; reads P.lit)
 }
-template <int S>
+template <int S, bool LIT>
 void launchRender(const RenderParams& P, hipStream_t st) {
     if (P.kernel == PT_KERNEL_WAVEFRONT && P.pixAcc)
-        renderKernelWF<S, true, false><<<P.nwaves, kWave, 0, st>>>(P);
+        renderKernelWF<S, true, false, false, LIT><<<P.nwaves, kWave, 0, st>>>(P);
     else if (P.kernel == PT_KERNEL_WAVEFRONT)
-        renderKernelWF<S, false, false><<<P.compatGrid, kWave, 0, st>>>(P);
-    else if (P.pixAcc) renderKernel<S, true><<<P.ntiles, kWave, 0, st>>>(P);
-    else renderKernel<S, false><<<P.ntiles, kWave, 0, st>>>(P);
+        renderKernelWF<S, false, false, false, LIT><<<P.compatGrid, kWave, 0, st>>>(P);
+    else if (P.pixAcc) renderKernel<S, true, LIT><<<P.ntiles, kWave, 0, st>>>(P);
+    else renderKernel<S, false, LIT><<<P.ntiles, kWave, 0, st>>>(P);
 }
 template <int S, bool WIDE, bool INST = false, bool SAMPLE = true>
 int wavesPerCU(int& n) {
@@ -3919,7 +3966,9 @@ template <class F>
 bool withBinStack(int stack, F f) { return withStack<16, 24, 32, 48, 64, 80>(stack, f); }
 
 // Waves per CU of the render kernel a launch runs: its occupancy (sample mode launches exactly the
-// waves that fit; compat launches do not ask).  The compat wide kernels live in pt_compat.hip's
+// waves that fit; compat launches do not ask).  Asked of the kernel without LIT: its LIT twin has
+// the same LDS and waves-per-SIMD attribute, so the same occupancy (DESIGN.md's resource table).
+// The compat wide kernels live in pt_compat.hip's
 // translation unit.
 int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample) {
     const bool wide = kernel == PT_KERNEL_WIDE;
@@ -3938,8 +3987,13 @@ int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample) 
 }
 int dispatchRender(int stack, const RenderParams& P, hipStream_t st) {
     const bool wide = P.kernel == PT_KERNEL_WIDE;
-    const bool ok = wide ? withWideStack(stack, [&](auto N) { launchRenderWide<decltype(N)::value>(P, st); })
-                         : withBinStack(stack, [&](auto N) { launchRender<decltype(N)::value>(P, st); });
+    const bool ok = wide ? withWideStack(stack, [&](auto N) {
+        constexpr int K = decltype(N)::value;
+        P.lit ? launchRenderWide<K, true>(P, st) : launchRenderWide<K, false>(P, st);
+    }) : withBinStack(stack, [&](auto N) {
+        constexpr int K = decltype(N)::value;
+        P.lit ? launchRender<K, true>(P, st) : launchRender<K, false>(P, st);
+    });
     if (!ok) return fail(PT_ERR_STATE, wide ? "unsupported wide BVH depth" : "unsupported BVH depth");
     HIP_TRY(hipGetLastError());
     return PT_OK;
@@ -4098,6 +4152,9 @@ int filmStats(pt_film* f, pt_stats* stats) {
 }  // namespace
 
 // ================================================================== C ABI (device part)
+// a radiance component (emissive materials, sky colours): finite and in [0, PT_MAX_RADIANCE]
+static bool radianceOk(float v) { return std::isfinite(v) && v >= 0.0f && v <= PT_MAX_RADIANCE; }
+
 extern "C" {
 
 int pt_device_count(int* count) {
@@ -4118,12 +4175,22 @@ int pt_scene_create(int device, const pt_object* objs, int64_t n, const pt_mater
             return fail(PT_ERR_INVALID, "pt_scene_create: unknown object type");
         if (objs[i].mat < 0 || objs[i].mat >= nmat) return fail(PT_ERR_INVALID, "pt_scene_create: material id out of range");
     }
+    bool emissive = false;
+    for (int64_t i = 0; i < nmat; i++) {   // (the other material types are taken as they come)
+        if (mats[i].type != PT_EMISSIVE) continue;
+        emissive = true;
+        for (int a = 0; a < 3; a++)
+            if (!radianceOk(mats[i].albedo[a]))
+                return fail(PT_ERR_INVALID, "pt_scene_create: emissive material " + std::to_string(i) + ": radiance[" +
+                                                std::to_string(a) + "] must be finite and in [0, PT_MAX_RADIANCE]");
+    }
     int rc = setDevice(device);
     if (rc) return rc;
     std::unique_ptr<pt_scene> s(new pt_scene);
     s->device = device;
     s->nobj = n;
     s->nmat = nmat;
+    s->hasEmissive = emissive;
     s->objs.assign(objs, objs + n);
     for (int64_t i = 0; i < n && !s->hasSpheres; i++) s->hasSpheres = objs[i].type == PT_SPHERE;
     // materials: (albedo.xyz, fuzz), (ir, type, 0, 0)
@@ -4141,6 +4208,19 @@ int pt_scene_create(int device, const pt_object* objs, int64_t n, const pt_mater
     if ((rc = devAlloc(s->dobjs, (size_t)std::max<int64_t>(1, n) * sizeof(pt_object)))) return rc;
     if (n > 0) HIP_TRY(hipMemcpy(s->dobjs.p, objs, (size_t)n * sizeof(pt_object), hipMemcpyHostToDevice));
     *out = s.release();
+    return PT_OK;
+}
+
+int pt_scene_set_sky(pt_scene* s, const float horizon[3], const float zenith[3]) {
+    if (!s || !horizon || !zenith) return fail(PT_ERR_INVALID, "pt_scene_set_sky: null argument");
+    for (int a = 0; a < 3; a++) {
+        if (!radianceOk(horizon[a]))
+            return fail(PT_ERR_INVALID, "pt_scene_set_sky: horizon[" + std::to_string(a) + "] must be finite and in [0, PT_MAX_RADIANCE]");
+        if (!radianceOk(zenith[a]))
+            return fail(PT_ERR_INVALID, "pt_scene_set_sky: zenith[" + std::to_string(a) + "] must be finite and in [0, PT_MAX_RADIANCE]");
+    }
+    // (host state only: the next pt_render copies it into its launch parameters)
+    for (int a = 0; a < 3; a++) { s->skyH[a] = horizon[a]; s->skyZ[a] = zenith[a]; }
     return PT_OK;
 }
 
@@ -4716,6 +4796,12 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     P.cam.right = make_float3(cam->right[0], cam->right[1], cam->right[2]);
     P.cam.up = make_float3(cam->up[0], cam->up[1], cam->up[2]);
     P.cam.lens = cam->lens_radius;
+    P.skyH = make_float3(s->skyH[0], s->skyH[1], s->skyH[2]);
+    P.skyZ = make_float3(s->skyZ[0], s->skyZ[1], s->skyZ[2]);
+    {   // the LIT kernels only where they are needed: an emitter, or a sky that is not the reference's
+        static const float H0[3] = {1.0f, 1.0f, 1.0f}, Z0[3] = {0.5f, 0.7f, 1.0f};
+        P.lit = (s->hasEmissive || std::memcmp(s->skyH, H0, sizeof(H0)) != 0 || std::memcmp(s->skyZ, Z0, sizeof(Z0)) != 0) ? 1 : 0;
+    }
     uint32_t* b = f->state.as<uint32_t>();
     P.sd = b; P.s0 = b + np; P.s1 = b + 2 * np; P.s2 = b + 3 * np; P.s3 = b + 4 * np; P.s4 = b + 5 * np;
     P.out = static_cast<float*>(dst);

@@ -206,6 +206,12 @@ pt_material dielectric(float ir) {
     m.ir = ir;
     return m;
 }
+pt_material emissive(const color& radiance) {
+    pt_material m{};
+    m.type = PT_EMISSIVE;
+    put3(m.albedo, radiance);
+    return m;
+}
 pt_object sphere(const point3& c, float r, int mat) {
     pt_object o{};
     o.type = PT_SPHERE;
@@ -254,7 +260,9 @@ static size_t appendMeshes(Scene& s, const objl::Loader& ld, float scale, const 
     return added;
 }
 
-static void cornellBox(Scene& s, const std::string& dir) {
+// lit: the lamp (light.obj) emits -- a PT_EMISSIVE material appended after the box's three -- instead
+// of being one more white rectangle (the "_lit" presets, meant for a black sky: pt_preset_sky).
+static void cornellBox(Scene& s, const std::string& dir, bool lit = false) {
     // Build-chosen materials (the reference ships geometry only).
     int white = (int)s.materials.size();
     s.materials.push_back(lambertian(color(0.725f, 0.71f, 0.68f)));
@@ -262,20 +270,34 @@ static void cornellBox(Scene& s, const std::string& dir) {
     s.materials.push_back(lambertian(color(0.63f, 0.065f, 0.05f)));
     int green = (int)s.materials.size();
     s.materials.push_back(lambertian(color(0.14f, 0.45f, 0.091f)));
+    int lamp = white;
+    if (lit) {
+        lamp = (int)s.materials.size();
+        s.materials.push_back(emissive(color(17.0f, 12.0f, 4.0f)));   // build-chosen, like the albedos
+    }
     const vec3 zero(0, 0, 0);
     appendObj(s, dir + "/cornellbox/floor.obj", 1.0f, zero, white);
     appendObj(s, dir + "/cornellbox/left.obj", 1.0f, zero, red);
     appendObj(s, dir + "/cornellbox/right.obj", 1.0f, zero, green);
-    appendObj(s, dir + "/cornellbox/light.obj", 1.0f, zero, white);
+    appendObj(s, dir + "/cornellbox/light.obj", 1.0f, zero, lamp);
     appendObj(s, dir + "/cornellbox/shortbox.obj", 1.0f, zero, white);
     appendObj(s, dir + "/cornellbox/tallbox.obj", 1.0f, zero, white);
 }
 
 static float aspectOf(int w, int h) { return (float)w / (float)h; }
 
-Scene buildPreset(const std::string& name, const std::string& dir, int width, int height) {
+// "cornell_lit" / "bunny_cornell_lit": the preset without the suffix, the lamp emissive
+static bool litPreset(const std::string& name, std::string& base) {
+    const bool lit = name == "cornell_lit" || name == "bunny_cornell_lit";
+    base = lit ? name.substr(0, name.size() - 4) : name;
+    return lit;
+}
+
+Scene buildPreset(const std::string& fullName, const std::string& dir, int width, int height) {
     Scene s;
-    s.name = name;
+    s.name = fullName;
+    std::string name;
+    const bool lit = litPreset(fullName, name);
     auto frame = [&](int w, int h, int spp, int depth) {
         s.width = width > 0 ? width : w;
         s.height = height > 0 ? height : h;
@@ -361,7 +383,7 @@ Scene buildPreset(const std::string& name, const std::string& dir, int width, in
         else if (name == "bunny_cornell") frame(1920, 1080, 1024, 50);
         else if (name == "bunny_field_x4") frame(1920, 1080, 128, 16);
         else frame(1920, 1080, 512, 16);
-        cornellBox(s, dir);
+        cornellBox(s, dir, lit);
         const int white = 0;
         if (name == "bunny_cornell") {
             // Build-chosen placement: x1500, resting on the floor in the free front-right
@@ -388,7 +410,7 @@ Scene buildPreset(const std::string& name, const std::string& dir, int width, in
         s.cam = camera(vec3(278, 273, -800), vec3(278, 273, 0), 40, aspectOf(s.width, s.height), 0, 10, 0.0f,
                        1.0f).abi();
     } else {
-        throw std::runtime_error("unknown preset '" + name + "'");
+        throw std::runtime_error("unknown preset '" + fullName + "'");
     }
     return s;
 }
@@ -493,14 +515,16 @@ int pt_camera_move(pt_camera* c, int dir, float dt) {
 int pt_preset_instanced(const char* name, const char* models_dir, int width, int height, pt_instanced_desc* out) {
     if (!name || !out) return fail(PT_ERR_INVALID, "pt_preset_instanced: null argument");
     std::memset(out, 0, sizeof(*out));
-    const std::string n = name, dir = models_dir ? models_dir : "models";
+    const std::string full = name, dir = models_dir ? models_dir : "models";
+    std::string n;
+    const bool lit = litPreset(full, n);
     if (n != "bunny_field" && n != "bunny_cornell" && n != "cornell")
-        return fail(PT_ERR_INVALID, "pt_preset_instanced: no instanced form of '" + n + "'");
+        return fail(PT_ERR_INVALID, "pt_preset_instanced: no instanced form of '" + full + "'");
     try {
         // the flat preset for the frame, camera and materials; the meshes rebuilt in object space
-        Scene flat = buildPreset(n, dir, width, height);
+        Scene flat = buildPreset(full, dir, width, height);
         Scene box, bunny;
-        cornellBox(box, dir);   // (its own materials: the same 3 as the flat preset's first ones)
+        cornellBox(box, dir, lit);   // (its own materials: the same as the flat preset's first ones)
         std::vector<pt_instance> inst;
         auto translate = [](float x, float y, float z, int mesh) {
             pt_instance i{};
@@ -585,6 +609,25 @@ int pt_preset_scene(const char* name, const char* models_dir, int width, int hei
         std::snprintf(out->name, sizeof(out->name), "%s", s.name.c_str());
     } catch (const std::exception& e) {
         return fail(PT_ERR_IO, std::string("pt_preset_scene: ") + e.what());
+    }
+    return PT_OK;
+}
+
+int pt_preset_sky(const char* name, float horizon[3], float zenith[3]) {
+    if (!name || !horizon || !zenith) return fail(PT_ERR_INVALID, "pt_preset_sky: null argument");
+    static const char* const known[] = {"triangle_world", "random_world", "test_world", "rtiow", "cornell",
+                                        "bunny_cornell", "bunny_field", "bunny_field_x4", "cornell_lit",
+                                        "bunny_cornell_lit"};
+    const std::string full = name;
+    bool found = false;
+    for (const char* k : known) found = found || full == k;
+    if (!found) return fail(PT_ERR_INVALID, "pt_preset_sky: unknown preset '" + full + "'");
+    std::string base;
+    if (litPreset(full, base)) {   // lit by the lamp alone
+        for (int a = 0; a < 3; a++) horizon[a] = zenith[a] = 0.0f;
+    } else {                       // the reference's gradient (main.cu:34-36)
+        horizon[0] = horizon[1] = horizon[2] = 1.0f;
+        zenith[0] = 0.5f; zenith[1] = 0.7f; zenith[2] = 1.0f;
     }
     return PT_OK;
 }

@@ -111,6 +111,7 @@ public:
 // Material constructors: material.h:21-26 (the overload is the type tag; metal fuzz clamps to 1).
 pt_material lambertian(const color& albedo);
 pt_material metal(const color& albedo, float fuzz);
+pt_material emissive(const color& radiance);
 pt_material dielectric(float ir);
 // CudaObj constructors: cuda_object.h:21-42.
 pt_object sphere(const point3& c, float r, int mat);

@@ -17,11 +17,13 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: pt_render_png [--scene NAME] [--models DIR] [--width W] [--height H] [--spp N]\n"
                  "                     [--depth D] [--seed S] [--gpus N] [--stripe ROWS] [--out FILE]\n"
-                 "                     [--rng compat|sample] [--frames K]\n"
+                 "                     [--rng compat|sample] [--frames K] [--sky default|black]\n"
                  "--frames K: progressive rendering, K frames of --spp samples accumulated per pixel (the\n"
                  "            headless counterpart of the reference's interactive loop); PNG of the last one\n"
+                 "--sky: the sky the scene is rendered under; without it the preset's own (pt_preset_sky):\n"
+                 "       black for the _lit scenes, whose lamp emits, the reference's gradient otherwise\n"
                  "scenes: triangle_world (default, as the reference), random_world, test_world, rtiow,\n"
-                 "        cornell, bunny_cornell, bunny_field\n");
+                 "        cornell, bunny_cornell, bunny_field, cornell_lit, bunny_cornell_lit\n");
 }
 
 #define CHECK(x)                                                                      \
@@ -34,7 +36,7 @@ static void usage() {
     } while (0)
 
 int main(int argc, char** argv) {
-    std::string scene = "triangle_world", models = "models", out = "debug.png";
+    std::string scene = "triangle_world", models = "models", out = "debug.png", sky;
     int width = 0, height = 0, spp = -1, depth = -1, gpus = 1, stripe = 8, frames = 1, rng = PT_RNG_COMPAT;
     unsigned long long seed = 1;
     for (int i = 1; i < argc; i++) {
@@ -54,6 +56,10 @@ int main(int argc, char** argv) {
         else if (a == "--stripe") stripe = std::atoi(next());
         else if (a == "--out") out = next();
         else if (a == "--frames") frames = std::atoi(next());
+        else if (a == "--sky") {
+            sky = next();
+            if (sky != "default" && sky != "black") { usage(); return 2; }
+        }
         else if (a == "--rng") {
             std::string r = next();
             if (r == "compat") rng = PT_RNG_COMPAT;
@@ -66,6 +72,11 @@ int main(int argc, char** argv) {
     CHECK(pt_preset_scene(scene.c_str(), models.c_str(), width, height, &d));
     if (spp > 0) d.spp = spp;
     if (depth >= 0) d.max_depth = depth;
+    // the sky: the preset's own, or --sky's ("default" = the reference's gradient, main.cu:34-36)
+    float horizon[3] = {1.0f, 1.0f, 1.0f}, zenith[3] = {0.5f, 0.7f, 1.0f};
+    if (sky.empty()) CHECK(pt_preset_sky(scene.c_str(), horizon, zenith));
+    if (sky == "black")
+        for (int a = 0; a < 3; a++) horizon[a] = zenith[a] = 0.0f;
     int ndev = 0;
     CHECK(pt_device_count(&ndev));
     if (ndev <= 0) { std::fprintf(stderr, "no GPU visible\n"); return 99; }
@@ -86,6 +97,7 @@ int main(int argc, char** argv) {
             pt_scene* s = nullptr;
             pt_film* f = nullptr;
             CHECK(pt_scene_create(g, d.objects, d.n_objects, d.materials, d.n_materials, &s));
+            CHECK(pt_scene_set_sky(s, horizon, zenith));
             CHECK(pt_scene_build_bvh(s, PT_BVH_ORIGIN_BOUNDS));
             CHECK(pt_film_create(g, d.width, d.height, stripe, gpus, g, seed, &f));
             int nrows = 0;

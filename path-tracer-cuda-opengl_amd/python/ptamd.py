@@ -20,7 +20,8 @@ MODELS_DIR = os.path.join(REPO, "models")
 
 PT_OK = 0
 PT_SPHERE, PT_TRIANGLE = 1, 3
-PT_LAMBERTIAN, PT_METAL, PT_DIELECTRIC = 1, 2, 4
+PT_LAMBERTIAN, PT_METAL, PT_DIELECTRIC, PT_EMISSIVE = 1, 2, 4, 8
+PT_MAX_RADIANCE = 1024.0   # bound of an emissive material's radiance and of the sky colours
 PT_BVH_ORIGIN_BOUNDS, PT_BVH_HOST_KEYS, PT_BVH_WIDE_DEVICE = 1, 2, 4
 
 # numpy mirrors of the C structs (all 4-byte fields, no padding)
@@ -91,7 +92,7 @@ EXPORTS = [
     "pt_scene_update_objects", "pt_trace_closest_ex", "pt_scene_wide_info", "pt_trace_closest_device",
     "pt_scene_build_bvh_ex", "pt_film_stats", "pt_preset_instanced", "pt_instanced_desc_free",
     "pt_scene_create_instanced", "pt_trace_occluded", "pt_trace_occluded_device",
-    "pt_scene_update_instances",
+    "pt_scene_update_instances", "pt_scene_set_sky", "pt_preset_sky",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -115,6 +116,8 @@ _sig = {
     "pt_camera_move": (C.c_int, [C.POINTER(Camera), C.c_int, C.c_float]),
     "pt_preset_scene": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(SceneDesc)]),
     "pt_scene_desc_free": (None, [C.POINTER(SceneDesc)]),
+    "pt_preset_sky": (C.c_int, [C.c_char_p, _P, _P]),
+    "pt_scene_set_sky": (C.c_int, [_P, _P, _P]),
     "pt_load_obj": (C.c_int, [C.c_char_p, C.c_float, _P, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "pt_free": (None, [_P]),
     "pt_morton_keys": (C.c_int, [_P, C.c_int64, C.c_int, _P]),
@@ -204,8 +207,16 @@ def camera_to_array(cam: Camera) -> np.ndarray:
     return np.frombuffer(bytes(cam), dtype=np.float32).copy()
 
 
+def preset_sky(name: str):
+    """pt_preset_sky: the (horizon, zenith) colours a preset is meant to be rendered under -- black for
+    the "_lit" presets, the reference's gradient otherwise; PtError for an unknown name."""
+    h, z = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    _check(lib.pt_preset_sky(name.encode(), _ptr(h), _ptr(z)), "pt_preset_sky")
+    return h, z
+
+
 class Preset:
-    """Host-side scene description produced by pt_preset_scene."""
+    """Host-side scene description produced by pt_preset_scene.  `sky`: see preset_sky()."""
 
     def __init__(self, name: str, width: int = 0, height: int = 0, models_dir: str = MODELS_DIR):
         d = SceneDesc()
@@ -220,6 +231,7 @@ class Preset:
             self.name = d.name.decode()
         finally:
             lib.pt_scene_desc_free(C.byref(d))
+        self.sky = preset_sky(name)
 
 
 def _copy_array(ptr, n, dtype):
@@ -246,6 +258,7 @@ class InstancedPreset:
             self.name = d.name.decode()
         finally:
             lib.pt_instanced_desc_free(C.byref(d))
+        self.sky = preset_sky(name)
 
     def flattened_count(self) -> int:
         return int(sum(self.mesh_count[i["mesh"]] for i in self.instances))
@@ -356,6 +369,15 @@ class Scene:
                "pt_scene_update_instances")
         self.instances = self.instances.copy()
         self.instances[first:first + len(inst)] = inst
+
+    def set_sky(self, horizon, zenith) -> None:
+        """pt_scene_set_sky: the colours a missed ray blends between (horizon at y = -1, zenith at
+        y = +1), for the renders enqueued from now on; no rebuild.  Components in [0, PT_MAX_RADIANCE]."""
+        h = None if horizon is None else np.ascontiguousarray(horizon, np.float32)
+        z = None if zenith is None else np.ascontiguousarray(zenith, np.float32)
+        assert (h is None or h.shape == (3,)) and (z is None or z.shape == (3,))
+        _check(lib.pt_scene_set_sky(self.h, None if h is None else _ptr(h), None if z is None else _ptr(z)),
+               "pt_scene_set_sky")
 
     @property
     def build_ms(self) -> float:
