@@ -202,7 +202,14 @@ int pt_scene_build_bvh_ex(pt_scene* scene, int flags, void* stream);
  * results equal the flattened scene's within floating-point tolerance (tests/test_gpu_instancing.py
  * states it), not bit for bit; ties between equal t are decided by (instance, primitive).  Hit
  * records report obj = the object's index in the flattened order (instances in order, each
- * contributing its mesh's objects). */
+ * contributing its mesh's objects).
+ * Handedness: front_face is decided in object space, by the mesh's own winding (a triangle's
+ * (v1 - v0) x (v2 - v0), a sphere's (p - c) / r), whatever the matrix.  So a mirrored instance
+ * (det of m's 3 x 3 part < 0) keeps its mesh's front side, and the flattened scene it equals is the
+ * one with v1 and v2 of each of its triangles swapped: a triangle transformed vertex by vertex has
+ * the normal det * A^-T (e1 x e2), the opposite side for det < 0, which would turn a dielectric
+ * inside out.  Against the plainly flattened vertices a mirrored instance returns the same t, p and
+ * n with front_face inverted on its triangles (tests/test_gpu_instance_affine.py pins the rule). */
 int pt_scene_create_instanced(int device, const pt_object* objs, int64_t n_objects, const int64_t* mesh_first,
                               const int64_t* mesh_count, int n_meshes, const pt_instance* instances, int64_t n_instances,
                               const pt_material* mats, int64_t n_materials, pt_scene** out);

@@ -19,7 +19,9 @@ pytestmark = pytest.mark.gpu
 
 
 def random_transforms(n, seed, reach=30.0):
-    """Rotations with uniform scales in [0.5, 2] and translations in +-reach."""
+    """Rotations with uniform scales in [0.5, 2] and translations in +-reach.  Proper rotations only
+    (LAPACK's QR of a 3 x 3 matrix returns det Q = +1): mirrors, stretches and shears live in
+    test_gpu_instance_affine.py."""
     rng = np.random.default_rng(seed)
     out = np.zeros((n, 12), np.float32)
     for i in range(n):

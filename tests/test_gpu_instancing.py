@@ -145,6 +145,9 @@ def test_identity_instances_bit_exact(pt, gpu):
 
 
 def random_transforms(n, seed):
+    """Rotations with uniform scales in [0.5, 2] and translations in +-30.  Proper rotations only
+    (LAPACK's QR of a 3 x 3 matrix returns det Q = +1): mirrors, stretches and shears live in
+    test_gpu_instance_affine.py."""
     rng = np.random.default_rng(seed)
     out = np.zeros((n, 12), np.float32)
     for i in range(n):
