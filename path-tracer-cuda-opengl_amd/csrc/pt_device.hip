@@ -72,6 +72,7 @@ struct DevScene {
     const float4* wnodes;    // compressed 8-wide nodes, 5 x float4 each (renderKernelWF<.., WIDE>; host/pt_wide8.cpp)
     const float4* wprims;    // primitive records in wide-tree leaf order, {v0, rank} {v1, objID} {v2, sphere}
     const float4* wshade;    // shading records in reference rank order (wide kernels)
+    const float4* wbox;      // exact triangle boxes in rank order, {mn.x, mx.x, mn.y, mx.y} {mn.z, mx.z, 0, 0} (deferredRedo)
     const uint32_t* rankOf;  // leaf k -> its rank in the reference's traversal order
     const int* iparent;      // parent of each internal LBVH node (-1 for the root)
     unsigned int* err;       // set (never cleared in-kernel) when a traversal guard trips
@@ -385,6 +386,9 @@ __device__ __forceinline__ SlabHit refLeafBox(const Prim& q, bool sphere, float3
 // SPH = false: the scene has no spheres (DevScene::hasSpheres), so neither q nor the current best
 // is one and the tie rule reduces to the triangles' ascending rank -- the same decisions with
 // fewer instructions.
+// This per-candidate form serves scenes with spheres, the instanced kernels (leafBoxes = false) and
+// the ray-query kernels; the non-instanced render kernels on triangle-only scenes decide the same
+// rule once per query (wideTestTri / deferredRedo below).
 template <bool SPH>
 __device__ __forceinline__ void wideTest(const Prim& q, float3 o, float3 d, float3 inv, float tmin, float& closest,
                                          int& best, float& bestLo, bool leafBoxes, bool& redo, uint32_t keyHi = 0u) {
@@ -413,6 +417,41 @@ __device__ __forceinline__ void wideTest(const Prim& q, float3 o, float3 d, floa
             }
         }
     }
+}
+
+// The same rule decided once per query instead of once per candidate (the non-instanced wide render
+// kernels on triangle-only scenes).  The loop keeps the plain minimum M of
+// (t, ascending rank) over the candidates and t2, the second-smallest candidate distance (an equal
+// t counts): closest <= t2 always, so t2' is the median of (t, closest, t2).  When the query ends,
+// deferredRedo tests M's exact box with tmax = inf.
+//  - A candidate inside its own box (lo <= t) is tested by the reference whenever it could improve
+//    the hit (its ancestors' boxes contain its box and the slab arithmetic is monotone, so they
+//    pass too) and is accepted iff t < closest.  If M is one, the reference ends with M: nothing
+//    before it holds a smaller or an equal-and-earlier t, nothing after it is closer.
+//  - M grazing (t_M < lo_M): the reference tests M iff its closest hit of that moment is >= lo_M,
+//    and every hit it can hold is a candidate with t >= t_M.  No other candidate in [t_M, lo_M),
+//    which is t2 >= lo_M: M is tested, accepted and final.  Otherwise the query is order-dependent.
+//  - A box the ray misses outright: the reference never tests M; order-dependent.
+// An order-dependent query is repeated in the reference's order (traceRefStackless), which is
+// exact by construction.  The running `closest` that culls nodes is >= t_M, and the wide planes lie
+// at least 2^emin outside the exact boxes, far beyond the rounding that opens a window [t, lo): M
+// and every candidate inside its window are visited (wideHits).
+__device__ __forceinline__ void wideTestTri(const Prim& q, float3 o, float3 d, float tmin, float& closest, int& best,
+                                            float& t2) {
+    const float t = primHitAny(q, false, o, d, tmin);
+    if (t >= 0.0f) {
+        const int k = (int)__float_as_uint(q.p0.w);
+        const bool better = t < closest || (t == closest && k < best);   // (t == closest: a finite hit, best >= 0)
+        t2 = __builtin_amdgcn_fmed3f(t, closest, t2);
+        closest = better ? t : closest;
+        best = better ? k : best;
+    }
+}
+// Is the finished query (closest, t2) order-dependent?  xy, z: the best hit's exact box (DevScene::wbox:
+// refLeafBox's planes as {mn, mx} pairs per axis), under refLeafBox's slab arithmetic.
+__device__ __forceinline__ bool deferredRedo(float4 xy, float2 z, float3 o, float3 inv, float closest, float t2) {
+    const SlabHit b = slabPair(v2f{xy.x, xy.y}, v2f{xy.z, xy.w}, v2f{z.x, z.y}, o, inv, 0.001f, __builtin_inff());
+    return !b.hit || (closest < b.lo && t2 < b.lo);
 }
 
 // One compressed 8-wide node (five 16-B words, layout in host/pt_wide8.cpp) against the ray:
@@ -1265,7 +1304,7 @@ __device__ __forceinline__ float3 ld3(const __attribute__((address_space(4))) fl
 __device__ __forceinline__ DevScene ldScene(KArgs k) {
     DevScene S;
     S.nodes = k->S.nodes; S.prims = k->S.prims; S.shade = k->S.shade; S.mats = k->S.mats;
-    S.wnodes = k->S.wnodes; S.wprims = k->S.wprims; S.wshade = k->S.wshade; S.rankOf = k->S.rankOf;
+    S.wnodes = k->S.wnodes; S.wprims = k->S.wprims; S.wshade = k->S.wshade; S.wbox = k->S.wbox; S.rankOf = k->S.rankOf;
     S.iparent = k->S.iparent; S.err = k->S.err; S.nprims = k->S.nprims;
     S.hasSpheres = k->S.hasSpheres;
     S.cx = k->S.cx; S.cy = k->S.cy; S.cz = k->S.cz; S.ext = k->S.ext;
@@ -1364,9 +1403,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     uint32_t sRays = 0, sVisits = 0, sTris = 0, sSph = 0, sPaths = 0;
 #ifdef PT_DIAG
     uint32_t itN = 0, itL = 0, itS = 0, sPops = 0, sRedo = 0;   // scheduler diagnostics (iterations per kind)
+    uint32_t sRedoMiss = 0;   // redone queries whose final hit's exact box the ray misses outright (deferredRedo)
     unsigned long long sSpecN = 0, sIdleN = 0;   // NODE steps: lanes waiting on primitives that have nodes left; lanes with no NODE work
-    unsigned long long sAvoid = 0, sHalf = 0;    // LEAF (wide): tests whose exact box misses at test time; lanes testing one primitive
-    unsigned long long sAvoidInf = 0, sParkT = 0, sParkA = 0;   // ... misses even with tmax = inf; tests / misses in parked groups
+    unsigned long long sHalf = 0, sParkT = 0;    // LEAF (wide): lanes testing one primitive; tests in parked groups
     unsigned long long cycN = 0, cycL = 0, cycS = 0, cycH = 0;   // and shader cycles per kind, loop head
     unsigned long long cycSh = 0, cycTk = 0, cycNp = 0, cycBr = 0;   // SHADE: shading, tasks, new path, ray start
 #define PT_DIAG_ADD(v, x) (v) += (x)
@@ -1390,7 +1429,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #pragma unroll
     for (int i = 0; i < LQ; i++) { qref[i] = 0u; lq[i] = 0.0f; }
     // wide tree traversal state (WIDE): node group, primitive group, ray octant (| 8: redo the
-    // query in the reference's order), the best hit's window end
+    // query in the reference's order), the best hit's window end (scenes with spheres, instanced
+    // scenes) or the second-smallest candidate distance t2 (triangle-only scenes: wideTestTri)
     uint32_t ng = 0u, tgBase = 0u, tg = 0u, oct = 0u;
     float bestLo = 0.0f;
     bool active = false;
@@ -1420,7 +1460,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             const uint32_t oc_ = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u); \
             oct = oc_;                                                                            \
             tg = 0u;                                                                              \
-            bestLo = -__builtin_inff();                                                           \
+            /* sphere scenes: the best hit's window end; triangle-only: t2 (wideTestTri) */        \
+            bestLo = INST || kargs()->S.hasSpheres ? -__builtin_inff() : __builtin_inff();         \
             ng = S.nprims > 0 ? (1u << oc_) : 0u;                                                 \
             /* only camera rays can start far from the scene (a bounce starts on a primitive), and  \
                they all start at the camera: one uniform flag, set on the host (wideFar) */     \
@@ -1467,7 +1508,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 sTris += (uint32_t)__popcll(__ballot(!isS_));                                     \
                 sSph += (uint32_t)__popcll(__ballot(isS_));                                       \
                 if (sph_) wideTest<true>(q_, o, d, inv, 0.001f, closest, best, bestLo, lb_, redo_, 0u); \
-                else wideTest<false>(q_, o, d, inv, 0.001f, closest, best, bestLo, lb_, redo_, 0u); \
+                else if (INST) wideTest<false>(q_, o, d, inv, 0.001f, closest, best, bestLo, lb_, redo_, 0u); \
+                else wideTestTri(q_, o, d, 0.001f, closest, best, bestLo);   /* (SHADE decides) */ \
             }                                                                                     \
             if ((ng & 0xffu) == 0u) {                                                             \
                 if (sp == 0) break;                                                               \
@@ -1856,18 +1898,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 const Prim q0{w0[0], w0[1], w0[2]}, q1{w1[0], w1[1], w1[2]};
                 bool redo = false;
 #ifdef PT_DIAG
-                {   // tests the reference would skip: the primitive's exact box misses with the
-                    // closest hit of this moment (its own leaf test, render_manager.h:107-123)
-                    const bool a0 = h0 && !refLeafBox(q0, __float_as_uint(q0.p2.w) != 0u, o, inv, 0.001f, closest).hit;
-                    const bool a1 = h1 && !refLeafBox(q1, __float_as_uint(q1.p2.w) != 0u, o, inv, 0.001f, closest).hit;
-                    sAvoid += (unsigned long long)(__popcll(__ballot(a0)) + __popcll(__ballot(a1)));
+                {
                     sHalf += (unsigned long long)__popcll(__ballot(h0 && !h1));
-                    const bool i0 = h0 && !refLeafBox(q0, __float_as_uint(q0.p2.w) != 0u, o, inv, 0.001f, __builtin_inff()).hit;
-                    const bool i1 = h1 && !refLeafBox(q1, __float_as_uint(q1.p2.w) != 0u, o, inv, 0.001f, __builtin_inff()).hit;
-                    sAvoidInf += (unsigned long long)(__popcll(__ballot(i0)) + __popcll(__ballot(i1)));
                     const bool pk = !INST && (oct & 64u) != 0u;
                     sParkT += (unsigned long long)(__popcll(__ballot(pk && h0)) + __popcll(__ballot(pk && h1)));
-                    sParkA += (unsigned long long)(__popcll(__ballot(pk && a0)) + __popcll(__ballot(pk && a1)));
                 }
 #endif
                 // (instanced: no reference leaf-box rule; the hit key carries the instance)
@@ -1880,8 +1914,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                     sTris += (uint32_t)__popcll(__ballot(h0 && !s0)) + (uint32_t)__popcll(__ballot(h1 && !s1));
                     sSph += (uint32_t)__popcll(__ballot(h0 && s0)) + (uint32_t)__popcll(__ballot(h1 && s1));
                 } else {
-                    if (h0) wideTest<false>(q0, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
-                    if (h1) wideTest<false>(q1, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
+                    if constexpr (INST) {
+                        if (h0) wideTest<false>(q0, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
+                        if (h1) wideTest<false>(q1, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
+                    } else {   // the leaf-box rule is decided once, in SHADE (bestLo holds t2)
+                        if (h0) wideTestTri(q0, o, d, 0.001f, closest, best, bestLo);
+                        if (h1) wideTestTri(q1, o, d, 0.001f, closest, best, bestLo);
+                    }
                     sTris += (uint32_t)__popcll(__ballot(h0)) + (uint32_t)__popcll(__ballot(h1));
                 }
                 if (redo) oct |= 8u;   // order-dependent candidate: repeat the query in the reference's order
@@ -1937,11 +1976,31 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         }
         if (kind == 2) {
             // ------------------------------------------------------------------ SHADE
-            if constexpr (WIDE) {
+            if constexpr (WIDE && !INST) {
+                bool redo = wantShade && !needTask && (oct & 8u);
+#ifdef PT_DIAG
+                bool missed = false;
+#endif
+                // Triangle-only scenes: the reference's leaf-box rule, decided here for the final
+                // hit alone (deferredRedo; bestLo holds t2)
+                if (!kargs()->S.hasSpheres && S.nprims > 1) {
+                    if (wantShade && !needTask && best >= 0 && !redo) {
+                        const float4* bx = kargs()->S.wbox + 2 * (size_t)best;
+                        redo = deferredRedo(bx[0], *reinterpret_cast<const float2*>(bx + 1), o, inv, closest, bestLo);
+#ifdef PT_DIAG
+                        {   // (which of them because the ray misses the final hit's box outright)
+                            const float2 bz_ = *reinterpret_cast<const float2*>(bx + 1);
+                            const float4 bx_ = bx[0];
+                            missed = !slabPair(v2f{bx_.x, bx_.y}, v2f{bx_.z, bx_.w}, v2f{bz_.x, bz_.y}, o, inv, 0.001f,
+                                               __builtin_inff()).hit;
+                        }
+#endif
+                    }
+                }
                 // rare: an order-dependent query (or a far origin), repeated in the reference's
                 // order.  Ranks index wshade.
-                const bool redo = !INST && wantShade && !needTask && (oct & 8u);
                 PT_DIAG_ADD(sRedo, (uint32_t)__popcll(__ballot(redo)));
+                PT_DIAG_ADD(sRedoMiss, (uint32_t)__popcll(__ballot(missed)));
                 if (redo) {
                     const DevScene S2 = ldScene(kargs());
                     closest = __builtin_inff();
@@ -2072,11 +2131,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         atomicAdd(P.counters + 20, (unsigned long long)sRedo);
         atomicAdd(P.counters + 21, sSpecN);
         atomicAdd(P.counters + 22, sIdleN);
-        atomicAdd(P.counters + 23, sAvoid);
+        atomicAdd(P.counters + 23, (unsigned long long)sRedoMiss);
         atomicAdd(P.counters + 25, sHalf);
-        atomicAdd(P.counters + 26, sAvoidInf);
         atomicAdd(P.counters + 27, sParkT);
-        atomicAdd(P.counters + 28, sParkA);
 #endif
     }
 }
@@ -3175,6 +3232,7 @@ struct pt_scene {
     DevBuf irange;                          // leaf range [first, last] per internal node
     DevBuf refitEvents;                     // refit phase 2 input: count, then crossing-node arrivals
     DevBuf wide, wprims, wshade, rankOf;    // compressed 8-wide tree, its primitive and shading records, leaf ranks (PT_KERNEL_WIDE)
+    DevBuf wbox;                            // exact primitive boxes in rank order (DevScene::wbox)
     std::unique_ptr<pt::WideDevBuilder> wideDev;   // device build scratch (PT_BVH_WIDE_DEVICE), kept between builds
     bool wideReady = false;                 // the wide tree matches the current LBVH build
     bool updated = false;                   // pt_scene_update_objects was called: a dynamic scene
@@ -3273,13 +3331,18 @@ int buildWide(pt_scene* s) {
     const std::vector<uint32_t> rank = pt::referenceRanks(refs.data() + 12, refs.data() + 13, 16, n);
     std::vector<uint32_t> wshade(shade.size());
     for (int64_t k = 0; k < n; k++) std::memcpy(&wshade[(size_t)rank[k] * 12], &shade[(size_t)k * 12], 48);
+    std::vector<float> wbox((size_t)n * pt::kW8BoxFloats);
+    for (int64_t k = 0; k < n; k++)
+        pt::exactTriBox(reinterpret_cast<const float*>(&prims[(size_t)k * pt::kW8PrimDwords]), &wbox[(size_t)rank[k] * pt::kW8BoxFloats]);
     pt::Wide8 w;
     std::string err;
     if (!pt::buildWide8(prims.data(), boxes.data(), rank.data(), n, w, err)) return fail(PT_ERR_STATE, err);
     int rc;
     if ((rc = devReserve(s->wide, w.nodes.size() * 4)) || (rc = devReserve(s->wprims, w.prims.size() * 4)) ||
-        (rc = devReserve(s->wshade, wshade.size() * 4)) || (rc = devReserve(s->rankOf, rank.size() * 4)))
+        (rc = devReserve(s->wshade, wshade.size() * 4)) || (rc = devReserve(s->rankOf, rank.size() * 4)) ||
+        (rc = devReserve(s->wbox, wbox.size() * 4)))
         return rc;
+    HIP_TRY(hipMemcpy(s->wbox.p, wbox.data(), wbox.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->wide.p, w.nodes.data(), w.nodes.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->wprims.p, w.prims.data(), w.prims.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->wshade.p, wshade.data(), wshade.size() * 4, hipMemcpyHostToDevice));
@@ -3297,12 +3360,13 @@ int buildWideDevice(pt_scene* s, hipStream_t st) {
     int rc;
     if ((rc = devReserve(s->wide, (size_t)pt::wideDevNodeSlots(n) * pt::kW8NodeDwords * 4)) ||
         (rc = devReserve(s->wprims, (size_t)n * pt::kW8PrimDwords * 4)) || (rc = devReserve(s->wshade, (size_t)n * 48)) ||
-        (rc = devReserve(s->rankOf, (size_t)n * 4)))
+        (rc = devReserve(s->rankOf, (size_t)n * 4)) || (rc = devReserve(s->wbox, (size_t)n * pt::kW8BoxFloats * 4)))
         return rc;
     if (!s->wideDev) s->wideDev.reset(new pt::WideDevBuilder);
     pt::WideDevIn in{s->prims.as<float4>(), s->shade.as<float4>(), s->leafBoxes.as<float>(), s->nodes.as<float4>(),
                      s->iparent.as<int>(), s->lparent.as<int>(), s->irange.as<int2>(), n};
-    pt::WideDevOut out{s->wide.as<uint32_t>(), s->wprims.as<uint32_t>(), s->wshade.as<float4>(), s->rankOf.as<uint32_t>()};
+    pt::WideDevOut out{s->wide.as<uint32_t>(), s->wprims.as<uint32_t>(), s->wshade.as<float4>(), s->wbox.as<float4>(),
+                       s->rankOf.as<uint32_t>()};
     std::string err;
     const hipError_t e = s->wideDev->build(in, out, st, err);
     if (e != hipSuccess) return fail(err.empty() ? PT_ERR_HIP : PT_ERR_STATE, err.empty() ? hipGetErrorString(e) : err);
@@ -4076,6 +4140,7 @@ DevScene devScene(const pt_scene* s) {
     S.wnodes = s->wide.as<float4>();
     S.wprims = s->wprims.as<float4>();
     S.wshade = s->wshade.as<float4>();
+    S.wbox = s->wbox.as<float4>();
     S.rankOf = s->rankOf.as<uint32_t>();
     S.iparent = s->iparent.as<int>();
     S.err = reinterpret_cast<unsigned int*>(s->counters.as<unsigned long long>() + 7);
@@ -4116,17 +4181,14 @@ void printIterStats(const unsigned long long* c, bool wide) {
                      (double)c[14] / std::max(1ull, c[10]), (double)c[12] / (double)(c[12] + c[13] + c[14]),
                      (double)c[13] / (double)(c[12] + c[13] + c[14]), (double)c[14] / (double)(c[12] + c[13] + c[14]));
     if (wide && c[8] > 0)
-        std::fprintf(stderr, "[pt] wide queries repeated in the reference order: %llu (lanes x steps); NODE steps: "
-                     "lanes waiting on primitives with nodes left %.1f, lanes without NODE work %.1f\n", c[20],
+        std::fprintf(stderr, "[pt] wide queries repeated in the reference order: %llu (lanes x steps; %llu for a final "
+                     "hit whose box the ray misses); NODE steps: "
+                     "lanes waiting on primitives with nodes left %.1f, lanes without NODE work %.1f\n", c[20], c[23],
                      (double)c[21] / std::max(1ull, c[8]), (double)c[22] / std::max(1ull, c[8]));
     if (wide && c[9] > 0)
-        std::fprintf(stderr, "[pt] LEAF: primitive tests whose exact box misses at test time %llu of %llu (%.3f); "
-                     "lanes testing one primitive per step %.1f\n", c[23], c[3] + c[2], (double)c[23] / std::max(1ull, c[2] + c[3]),
-                     (double)c[25] / std::max(1ull, c[9]));
-    if (wide && c[9] > 0)
-        std::fprintf(stderr, "[pt] LEAF: exact box misses even with tmax = inf %llu (%.3f of tests); tests in groups that "
-                     "were parked %llu (%.3f), their misses %llu\n", c[26], (double)c[26] / std::max(1ull, c[2] + c[3]),
-                     c[27], (double)c[27] / std::max(1ull, c[2] + c[3]), c[28]);
+        std::fprintf(stderr, "[pt] LEAF: lanes testing one primitive per step %.1f; tests in groups that were parked "
+                     "%llu (%.3f)\n", (double)c[25] / std::max(1ull, c[9]), c[27],
+                     (double)c[27] / std::max(1ull, c[2] + c[3]));
     if (c[15] > 0)
         std::fprintf(stderr, "[pt] loop head (choice of the step kind) cycles/iteration %.0f\n",
                      (double)c[15] / std::max(1ull, c[8] + c[9] + c[10]));
@@ -4479,7 +4541,8 @@ int pt_scene_bvh_info(pt_scene* s, int* depth, int64_t* nodes, int64_t* bytes) {
     if (!s->built) return fail(PT_ERR_STATE, "BVH not built");
     if (depth) *depth = s->depth;
     if (nodes) *nodes = s->nobj > 0 ? 2 * s->nobj - 1 : 0;
-    if (bytes) *bytes = (int64_t)s->deviceBytes;
+    // (+ the wide kernels' exact-box array once the wide tree exists)
+    if (bytes) *bytes = (int64_t)(s->deviceBytes + (s->wideReady && !s->instanced ? (size_t)s->nobj * pt::kW8BoxFloats * 4 : 0));
     return PT_OK;
 }
 

@@ -77,13 +77,19 @@ __global__ void rankKernel(const float4* __restrict__ lbvh, const int* __restric
     rank[k] = r;
 }
 
-__global__ void shadeByRankKernel(const float4* __restrict__ shade, const uint32_t* __restrict__ rank, int n, float4* wshade) {
+// (and the exact box of each record's three vertices, the layout and arithmetic of exactTriBox)
+__global__ void shadeByRankKernel(const float4* __restrict__ shade, const float4* __restrict__ prims,
+                                  const uint32_t* __restrict__ rank, int n, float4* wshade, float4* wbox) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const size_t r = rank[k];
     wshade[3 * r] = shade[3 * (size_t)k];
     wshade[3 * r + 1] = shade[3 * (size_t)k + 1];
     wshade[3 * r + 2] = shade[3 * (size_t)k + 2];
+    const float4 a = prims[3 * (size_t)k], b = prims[3 * (size_t)k + 1], c = prims[3 * (size_t)k + 2];
+    wbox[2 * r] = make_float4(fminf(fminf(a.x, b.x), c.x), fmaxf(fmaxf(a.x, b.x), c.x), fminf(fminf(a.y, b.y), c.y),
+                              fmaxf(fmaxf(a.y, b.y), c.y));
+    wbox[2 * r + 1] = make_float4(fminf(fminf(a.z, b.z), c.z), fmaxf(fmaxf(a.z, b.z), c.z), 0.0f, 0.0f);
 }
 
 // ---------------------------------------------------------------------------------- PLOC
@@ -1519,7 +1525,7 @@ hipError_t WideDevBuilder::build(const WideDevIn& in, WideDevOut& out, hipStream
 
     // 1. ranks, shading records in rank order
     rankKernel<<<blocks(n, tb), tb, 0, st>>>(in.lbvh, in.iparent, in.lparent, in.irange, (int)n, out.rank);
-    shadeByRankKernel<<<blocks(n, tb), tb, 0, st>>>(in.shade, out.rank, (int)n, out.wshade);
+    shadeByRankKernel<<<blocks(n, tb), tb, 0, st>>>(in.shade, in.prims, out.rank, (int)n, out.wshade, out.wbox);
     WB_TRY(hipGetLastError());
 
     // 2. the binary tree

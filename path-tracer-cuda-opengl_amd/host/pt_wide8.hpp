@@ -6,6 +6,7 @@
 // node, child boxes quantised outward to 8 bits per plane.  It changes which nodes are visited
 // and in which order, never which primitive is the closest hit ("Wide tree").
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -18,6 +19,18 @@ namespace pt {
 constexpr int kW8NodeDwords = PT_NODE_DWORDS;   // node slot in dwords: 80-B record (layout in pt_wide8.cpp) + padding
 static_assert(kW8NodeDwords == 20 || kW8NodeDwords == 32, "node slots of 80 or 128 B");
 constexpr int kW8PrimDwords = 12;   // 48-B primitive record
+constexpr int kW8BoxFloats = 8;     // exact-box record per rank: {mn.x, mx.x, mn.y, mx.y} {mn.z, mx.z, 0, 0}
+
+// The exact box of a triangle record {v0, .}{v1, .}{v2, .} as the reference's leaf test sees it
+// (min / max of the vertices in their order, utils::unionPoints), in the render kernels' slab
+// layout.  Only triangle-only scenes read it (a sphere record gives a box nobody uses).
+inline void exactTriBox(const float* rec, float* out) {
+    for (int a = 0; a < 3; a++) {
+        out[2 * a] = std::fmin(std::fmin(rec[a], rec[4 + a]), rec[8 + a]);
+        out[2 * a + 1] = std::fmax(std::fmax(rec[a], rec[4 + a]), rec[8 + a]);
+    }
+    out[6] = out[7] = 0.0f;
+}
 
 // The builders' smallest plane quantum is 2^-kW8EminShift of the larger of the scene's extent and
 // its coordinates; the traversal sends a ray whose origin lies farther than kW8FarExt scene extents

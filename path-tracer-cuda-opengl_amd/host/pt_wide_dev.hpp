@@ -32,6 +32,7 @@ struct WideDevOut {
     uint32_t* nodes;           // node slots x kW8NodeDwords dwords, capacity wideDevNodeSlots(n)
     uint32_t* wprims;          // n x 12 dwords
     float4* wshade;            // n x 3 float4, shading records in reference rank order
+    float4* wbox;              // n x 2 float4, exact triangle boxes in rank order (pt_wide8.hpp exactTriBox)
     uint32_t* rank;            // n: leaf k -> its rank in the reference's traversal order
     int depth = 0;             // wide levels (root = 1)
     int64_t slots = 0;         // node slots written
