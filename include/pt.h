@@ -326,6 +326,12 @@ int pt_render(pt_scene* scene, pt_film* film, const pt_camera* cam, int spp, int
  *   pixel's blocks are added exactly (integer atomics: the order in which blocks finish does not
  *   matter).  (pixel, block) tasks are handed to persistent waves, longest tiles first from the
  *   previous launch's costs; neither the scheduling nor the stripe partition changes the image.
+ *   Limits (PT_ERR_INVALID beyond them, nothing rendered): the film's width and rows below 65536, and
+ *   tiles x blocks x 64 < 2^32 - 2^26 tasks, with tiles = ceil(width / 8) * ceil(rows / 8) of the film's
+ *   own rows and blocks = ceil(spp / chunk) -- raise `chunk` for more samples.  (The tasks come from a
+ *   32-bit counter that every persistent wave pushes on by one pool of 64 after the last task; the
+ *   2^26 is room for 2^20 such waves, whatever the device.  A launch of more waves than that, which
+ *   no current device reaches, is PT_ERR_STATE.)
  *   Deterministic, statistically identical to the reference, not its random numbers; does not
  *   advance the film's XORWOW streams.  Needs 32 bytes of device memory per pixel
  *   ({x, y, z, rays} accumulators), whatever the spp.

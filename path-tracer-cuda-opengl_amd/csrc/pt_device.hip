@@ -5019,13 +5019,21 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
         P.blockShift = (P.block & (P.block - 1)) == 0 ? __builtin_ctz((unsigned)P.block) : -1;
         P.span = P.block;   // one summation block per task
         P.ngroups = P.nblocks;
+        const uint64_t ntasks = (uint64_t)P.ntiles * (uint64_t)P.ngroups * 64u;
+        // The 32-bit task counter (PT_TAKE_TASKS) runs past ntasks: every persistent wave takes
+        // exactly one pool of kTaskPool = 64 after the tasks are gone (its lanes each ask once more
+        // and share it), so the counter ends at ntasks + 64 * nwaves and must not wrap on the way --
+        // a wrapped grab would hand out task 0 again.  The limit leaves room for kMaxPersistentWaves
+        // such pools whatever the device (pt.h states it); the launch's nwaves is checked below.
+        constexpr uint64_t kMaxPersistentWaves = 1ull << 20;
+        constexpr uint64_t kTaskLimit = (1ull << 32) - (uint64_t)kTaskPool * kMaxPersistentWaves;   // 2^32 - 2^26
+        if (ntasks >= kTaskLimit)
+            return fail(PT_ERR_INVALID, "sample mode: too many (pixel, block) tasks (tiles x blocks x 64 must stay "
+                                        "below 2^32 - 2^26); raise the block size (chunk)");
+        P.ntasks = (uint32_t)ntasks;
         if ((rc = devReserve(f->pixAcc, (size_t)np * 32))) return rc;   // {x, y, z, rays} per pixel
         HIP_TRY(hipMemsetAsync(f->pixAcc.p, 0, (size_t)np * 32, st));
         P.pixAcc = f->pixAcc.as<unsigned long long>();
-        const uint64_t ntasks = (uint64_t)P.ntiles * (uint64_t)P.ngroups * 64u;
-        if (ntasks >= (1ull << 32) - 4096)
-            return fail(PT_ERR_INVALID, "sample mode: too many (pixel, block) tasks; raise the block size (chunk)");
-        P.ntasks = (uint32_t)ntasks;
         if (!f->taskCounter.p && (rc = devAlloc(f->taskCounter, 64))) return rc;
         HIP_TRY(hipMemsetAsync(f->taskCounter.p, 0, 4, st));
         P.taskCounter = f->taskCounter.as<unsigned>();
@@ -5033,6 +5041,8 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
         if ((rc = perCUFor(perCU))) return rc;
         const uint64_t full = (uint64_t)f->cus * (uint64_t)std::max(1, perCU);
         P.nwaves = (int)std::min<uint64_t>(full, (ntasks + 63) / 64);
+        if ((uint64_t)P.nwaves > kMaxPersistentWaves)
+            return fail(PT_ERR_STATE, "sample mode: more persistent waves than the task limit leaves room for");
         if (std::getenv("PT_ITER_STATS"))
             std::fprintf(stderr, "[pt] persistent waves %d (%d per CU, stack %d)\n", P.nwaves, perCU, stack);
         // Tile costs (rays of the tile's most expensive pixel) are measured on the first frame and

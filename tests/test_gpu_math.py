@@ -64,3 +64,23 @@ def test_hand_written_radix_sort_and_scans():
     out = subprocess.run([check], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert out.stdout.strip().splitlines()[-1] == "ok"
+
+
+@pytest.mark.gpu
+def test_fixed_point_conversions_equal_plain_references():
+    """Sample mode's conversions (pt_math.hpp), tools/micro/fixed_check.hip: blockFixed(x) for all
+    2^32 fp32 patterns -- negatives, +-0, denormals, block sums >= 2^24, +-inf, NaN -- equals the
+    oracle's rule evaluated in fp64, where x * 2^32 is exact (NaN -> 0, clamp to +-2^62, truncate);
+    fixedToFloat equals the same expression on the host at the int64 edges (0, +-1, around 2^32 and
+    2^53, +-2^62, INT64_MIN / MAX) and for 2^24 values of every magnitude.  Tolerance: none."""
+    check = os.path.join(REPO, "tools", "micro", "fixed_check")
+    assert os.path.exists(check), "tools/micro/fixed_check not built (make -C path-tracer-cuda-opengl_amd)"
+    out = subprocess.run([check], capture_output=True, text=True, timeout=120)
+    assert out.returncode in (0, 1), out.stderr
+    res = json.loads(out.stdout.strip().splitlines()[-1])
+    print(res)
+    assert res["block_fixed_checked"] == 2 ** 32
+    assert res["block_fixed_mismatches"] == 0, hex(res["block_fixed_first_mismatch"])
+    assert res["fixed_to_float_edges"] == 15 and res["fixed_to_float_edge_mismatches"] == 0
+    assert res["fixed_to_float_random"] == 2 ** 24 and res["fixed_to_float_random_mismatches"] == 0
+    assert out.returncode == 0
