@@ -137,6 +137,27 @@ struct Xorwow {
     __device__ __forceinline__ float uniform() { return uniformOf(next()); }
     // 2 * (uniform() - 0.5f): the unit-sphere coordinates (one exact FMA, pt_math.hpp)
     __device__ __forceinline__ float centered2() { return centered2Of(uniform()); }
+    // centered2() three times (x, y, z in order): the same draws with the state's rotation by three
+    // words written out, so a rejection-loop trial moves two state words (v3, v4), not five
+    __device__ __forceinline__ float3 centered2x3() {
+        uint32_t t0 = v0 ^ (v0 >> 2), t1 = v1 ^ (v1 >> 2), t2 = v2 ^ (v2 >> 2);
+        // (empty asm: an order for the scheduler -- the old v0, v1, v2 are dead before the new words
+        // are written, and d steps after its uses -- so the new words take the old ones' registers)
+        asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2));
+        // (the two moves written out where the old v0 and v1 are free: copies left to the register
+        // allocator land at the loop's ends and take a third and a fourth to get there)
+        uint32_t r0, r1;
+        asm volatile("v_mov_b32 %0, %1" : "=v"(r0) : "v"(v3));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(r1) : "v"(v4));
+        const uint32_t n0 = __builtin_amdgcn_bitop3_b32(v4, v4 << 4, t0 ^ (t0 << 1), 0x96);
+        const uint32_t n1 = __builtin_amdgcn_bitop3_b32(n0, n0 << 4, t1 ^ (t1 << 1), 0x96);
+        const uint32_t n2 = __builtin_amdgcn_bitop3_b32(n1, n1 << 4, t2 ^ (t2 << 1), 0x96);
+        uint32_t x0 = n0 + (d + 362437u), x1 = n1 + (d + 2u * 362437u);
+        asm volatile("" : "+v"(x0), "+v"(x1));
+        d += 3u * 362437u;
+        v0 = r0; v1 = r1; v2 = n0; v3 = n1; v4 = n2;
+        return f3(centered2Of(uniformOf(x0)), centered2Of(uniformOf(x1)), centered2Of(uniformOf(n2 + d)));
+    }
 };
 
 // Sample mode stream of (pixel p, sample s): one Philox4x32-10 block (Salmon et al. 2011)
@@ -812,10 +833,7 @@ __device__ __forceinline__ float3 onUnitSphere(G& g) {
     float3 res;
     float norm;
     do {   // draws x, y, z in order; centered2() = 2 * (uniform() - 0.5f) exactly
-        const float a = g.centered2();
-        const float b = g.centered2();
-        const float cz = g.centered2();
-        res = f3(a, b, cz);
+        res = g.centered2x3();
         norm = len2(res);
     } while (norm >= 1.0f);
     return divs(res, sqrtf(norm));
@@ -824,10 +842,7 @@ template <class G>
 __device__ __forceinline__ float3 inUnitSphere(G& g) {
     float3 res;
     do {
-        const float a = g.centered2();
-        const float b = g.centered2();
-        const float cz = g.centered2();
-        res = f3(a, b, cz);
+        res = g.centered2x3();
     } while (len2(res) >= 1.0f);
     return res;
 }
@@ -1295,6 +1310,10 @@ __device__ __forceinline__ KArgs kargs() {
     return k;
 }
 
+// The lane's bit of a wave-uniform mask as its predicate: no instruction of its own (the mask
+// becomes the vcc of the v_cndmask or the exec of the branch that uses it).
+__device__ __forceinline__ bool laneOf(uint64_t waveMask) { return __builtin_amdgcn_inverse_ballot_w64(waveMask); }
+
 typedef const __attribute__((address_space(4))) float KFloat;
 typedef const __attribute__((address_space(4))) uint32_t* KU32;   // read-only launch tables, scalar loads
 __device__ __forceinline__ float3 ld3(const __attribute__((address_space(4))) float3& v) {
@@ -1433,11 +1452,16 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     // scenes) or the second-smallest candidate distance t2 (triangle-only scenes: wideTestTri)
     uint32_t ng = 0u, tgBase = 0u, tg = 0u, oct = 0u;
     float bestLo = 0.0f;
-    bool active = false;
+    // Scheduler predicates are wave masks (one bit per lane, an SGPR pair each), combined with
+    // scalar logic and turned back into a lane predicate by laneOf() where a step needs one: a
+    // __ballot of a bool that went through && / || or a join costs two VALU (v_cndmask 0, 1 and
+    // v_cmp_ne) to rebuild a mask that already exists, so only plain integer compares are balloted.
+    const uint64_t allM = __ballot(true);
+    uint64_t activeM = 0;   // lanes on a path
     // sample mode task state: summation block, its tile (cost accounting), rays traced for it
     uint32_t depthPaths = 0;
     uint32_t pxRays = 0;   // compat tile / critical lanes: rays traced for the lane's pixel (P.pixRays)
-    bool needTask = SAMPLE;
+    uint64_t needTaskM = SAMPLE ? allM : 0;   // sample mode: lanes waiting for a task
     uint32_t poolBase = 0u, poolLeft = 0u;   // sample mode: the wave's reserved tasks (uniform)
 
 
@@ -1534,17 +1558,19 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         }                                                                                         \
         if (redo_) oct |= 8u;   /* order-dependent candidate: SHADE repeats the query */           \
     } while (0)
-    // Sample mode: lanes with needTask take the next tasks of the wave's pool, in lane order; an
+    // Sample mode: the lanes of needTaskM take the next tasks of the wave's pool, in lane order; an
     // empty pool is refilled with the next kTaskPool tasks of the global counter (one returning
     // atomic, whose latency the wave waits out, per kTaskPool tasks instead of per SHADE step).
     // Task t = (tile slot t / 64 / nblocks in launch order, block (t / 64) % nblocks, pixel
-    // t % 64 of the 8x8 tile); tasks off the frame edge are skipped.  Sets `got` for lanes
-    // that received a task; lanes that find the counter exhausted stop asking.
+    // t % 64 of the 8x8 tile); tasks off the frame edge are skipped.  Sets the bits of `got` for
+    // lanes that received a task; lanes that find the counter exhausted stop asking.  Every lane
+    // decodes a task (the same instructions whatever the exec mask); who took one, ran out or fell
+    // off the frame is wave masks.
 #define PT_TAKE_TASKS(got)                                                                          \
     do {                                                                                          \
         const auto& Q_ = *kargs();                                                                \
         for (;;) {                                                                                \
-            const uint64_t m_ = __ballot(needTask);                                               \
+            const uint64_t m_ = needTaskM;                                                        \
             if (m_ == 0) break;                                                                   \
             if (poolLeft == 0u) { /* refill the wave's pool: one returning atomic per kTaskPool */ \
                 const int leader_ = __ffsll((unsigned long long)m_) - 1;                          \
@@ -1576,35 +1602,31 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             const uint32_t txA_ = xyA_ & 0xffffu, tyA_ = xyA_ >> 16;                              \
             const uint32_t txB_ = xyB_ & 0xffffu, tyB_ = xyB_ >> 16;                              \
             const uint32_t k_ = (uint32_t)__popcll(m_ & ((1ull << lane) - 1ull));                 \
-            if (needTask && k_ < take_) {                                                         \
-                if (base_ + k_ >= Q_.ntasks) {                                                     \
-                    needTask = false;                                                             \
-                } else {                                                                          \
-                    const uint32_t o_ = off_ + k_, px_ = o_ & 63u;                                \
-                    const bool hi_ = o_ >= 64u;                                                   \
-                    const int c_ = (int)((hi_ ? txB_ : txA_) * 8u + (px_ & 7u));                  \
-                    const int r_ = (int)((hi_ ? tyB_ : tyA_) * 8u + (px_ >> 3));                  \
-                    if (c_ < Q_.width && r_ < Q_.nrows) {                                           \
-                        needTask = false;                                                         \
-                        got = true;                                                               \
-                        const uint32_t s0_ = (hi_ ? blkB_ : blkA_) * (uint32_t)Q_.span;           \
-                        taskState[lane] = make_uint4((uint32_t)c_ | ((uint32_t)r_ << 16), s0_,     \
-                                                     min(s0_ + (uint32_t)Q_.span, (uint32_t)Q_.spp), 0u); \
-                        sum = f3(0.0f, 0.0f, 0.0f);                                               \
-                    }                                                                             \
-                }                                                                                 \
+            const uint32_t o_ = off_ + k_, px_ = o_ & 63u;                                        \
+            const bool hi_ = o_ >= 64u;                                                           \
+            const int c_ = (int)((hi_ ? txB_ : txA_) * 8u + (px_ & 7u));                          \
+            const int r_ = (int)((hi_ ? tyB_ : tyA_) * 8u + (px_ >> 3));                          \
+            const uint64_t took_ = m_ & __ballot(k_ < take_);                                     \
+            const uint64_t left_ = took_ & __ballot(base_ + k_ < Q_.ntasks);                      \
+            const uint64_t in_ = left_ & __ballot(c_ < Q_.width) & __ballot(r_ < Q_.nrows);       \
+            needTaskM &= ~((took_ & ~left_) | in_);                                               \
+            got |= in_;                                                                           \
+            if (laneOf(in_)) {                                                                    \
+                const uint32_t s0_ = (hi_ ? blkB_ : blkA_) * (uint32_t)Q_.span;                   \
+                taskState[lane] = make_uint4((uint32_t)c_ | ((uint32_t)r_ << 16), s0_,             \
+                                             min(s0_ + (uint32_t)Q_.span, (uint32_t)Q_.spp), 0u); \
+                sum = f3(0.0f, 0.0f, 0.0f);                                                       \
             }                                                                                     \
         }                                                                                         \
     } while (0)
     // Sample mode: the lane's block (= its task; ts = the task state) is complete: its sum and ray
     // count go to the pixel's accumulator (order-free integer atomics on per-pixel addresses: no
     // contention; right here -- deferring them to a later step of the loop, where fewer registers
-    // are live, measured 2.6 % slower), and the lane asks for its next task.
+    // are live, measured 2.6 % slower); the caller moves the lane's bit to needTaskM.
 #define PT_FINISH_TASK(ts)                                                                          \
     do {                                                                                          \
         unsigned long long* acc_ = kargs()->pixAcc + 4 * (size_t)(((ts).x >> 16) * (uint32_t)kargs()->width + ((ts).x & 0xffffu)); \
         addBlock(acc_, sum, (ts).w + 1u, kargs()->measureCost != 0);                              \
-        needTask = true;                                                                          \
     } while (0)
     // New camera sample: main.cu:284-286 + camera::get_ray (lens sample: lensOffset; time draw skipped).
 #define PT_NEW_PATH()                                                                               \
@@ -1634,15 +1656,16 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 
     bool started = false;
     if constexpr (SAMPLE) {
-        // Every lane starts with needTask: the first loop iteration is a SHADE step that hands
+        // Every lane starts in needTaskM: the first loop iteration is a SHADE step that hands
         // out tasks.  max_depth <= 0 (no bounce: each sample is the sky colour of its camera
         // ray) is handled here, without the loop.
         if (P.max_depth <= 0) {
             for (;;) {
-                bool got = false;
+                uint64_t got = 0;
                 PT_TAKE_TASKS(got);
-                if (__ballot(got) == 0) break;
-                if (got) {
+                if (got == 0) break;
+                needTaskM |= got;   // (each of them ends its task below)
+                if (laneOf(got)) {
                     uint4 ts = taskState[lane];
                     depthPaths += ts.z - ts.y;
                     while (ts.y < ts.z) {
@@ -1650,12 +1673,14 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                         PT_NEW_PATH();
                         sum = add(sum, PT_SKY());
                         ts.y++;
-                        if (ts.y < ts.z) (void)kargs();   // (see the SHADE step's note on this read)
+                        // (a kernarg pointer re-read with no user -- kargs' empty asm is volatile --
+                        // that the register assignment of the sample kernels was measured with)
+                        if (ts.y < ts.z) (void)kargs();
                     }
                     PT_FINISH_TASK(ts);
                 }
             }
-            needTask = false;
+            needTaskM = 0;
             waveReduceAdd(P.counters + 4, depthPaths);   // (paths counted per lane here)
         }
     } else if (valid) {
@@ -1667,12 +1692,12 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         } else if (nSamples > 0) {
             PT_NEW_PATH();
             PT_BEGIN_RAY();
-            active = true;
             started = true;
         }
     }
-    sRays += (uint32_t)__popcll(__ballot(started));
-    sPaths += (uint32_t)__popcll(__ballot(started)) +
+    activeM = __ballot(started);   // (once per wave)
+    sRays += (uint32_t)__popcll(activeM);
+    sPaths += (uint32_t)__popcll(activeM) +
               (!SAMPLE && P.max_depth <= 0 ? (uint32_t)__popcll(__ballot(valid)) * (uint32_t)nSamples : 0u);
 
     for (;;) {
@@ -1681,18 +1706,23 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #endif
         // binary: room for both children's leaves in the queue; wide: nodes left, and no primitives
         // pending or (speculative traversal) room to park them.  Instanced kernels never park
-        // (SPEC is false there), so their second term is constant false; it stays because the
-        // compiler lays the step selection out around it: without it the instanced kernels come
-        // out 10 instructions shorter with other register assignments, a change to measure first.
-        const bool wantNode = WIDE ? (INST ? ((tg == 0u && ((ng & 0xffu) != 0u || sp > 0)) ||
-                                              (SPEC && tg != 0u && (ng & 0xffu) != 0u))
-                                           : ((SPEC ? (tg == 0u || ((oct >> 4) & 3u) < (uint32_t)SPECN) : tg == 0u) &&
-                                              ((ng & 0xffu) != 0u || sp > 0)))
-                                   : (node >= 0 && qn <= LQ - 2);
-        const bool wantLeaf = WIDE ? tg != 0u : qn > 0;
-        const bool wantShade = (active && (WIDE ? (tg == 0u && (ng & 0xffu) == 0u && sp == 0) : (node == -1 && qn == 0))) ||
-                               needTask;
-        const uint64_t mN = __ballot(wantNode), mL = __ballot(wantLeaf), mS = __ballot(wantShade);
+        // (SPEC is false there).  One ballot per integer compare, the rest is scalar logic.
+        uint64_t mN, mL, mS;
+        if constexpr (WIDE) {
+            const uint64_t noPrims = __ballot(tg == 0u);
+            const uint64_t nodesLeft = __ballot(((ng & 0xffu) | (uint32_t)sp) != 0u);   // (sp >= 0)
+            uint64_t mayVisit = noPrims;
+            if constexpr (SPEC)
+                mayVisit |= __ballot(SPECN == 1 ? (oct & 48u) == 0u : ((oct >> 4) & 3u) < (uint32_t)SPECN);
+            mN = mayVisit & nodesLeft;
+            mL = allM & ~noPrims;
+            mS = (activeM & noPrims & ~nodesLeft) | needTaskM;
+        } else {
+            const uint64_t inTree = __ballot(node >= 0), queued = __ballot(qn > 0);   // (node >= -1)
+            mN = inTree & (LQ == 2 ? allM & ~queued : __ballot(qn <= LQ - 2));
+            mL = queued;
+            mS = (activeM & ~inTree & ~queued) | needTaskM;
+        }
         if ((mN | mL | mS) == 0) break;
         const int nN = __popcll(mN), nL = __popcll(mL), nS = __popcll(mS);
         int kind;   // 0 node, 1 leaf, 2 shade
@@ -1710,6 +1740,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             // ------------------------------------------------------------------ NODE
             sVisits += (uint32_t)nN;
             PT_DIAG_ADD(itN, 1u);
+            const bool wantNode = laneOf(mN);
             if constexpr (WIDE) {
                 PT_DIAG_ADD(sSpecN, (unsigned long long)__popcll(__ballot(tg != 0u && ((ng & 0xffu) != 0u || sp > 0))));
                 PT_DIAG_ADD(sIdleN, (unsigned long long)(64 - nN));
@@ -1779,7 +1810,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 }
             } else if constexpr (WIDE) {
                 if (wantNode) {
-                    if (SPEC && tg != 0u) {   // park the waiting primitive group, keep traversing
+                    if (SPEC && laneOf(mL)) {   // park the waiting primitive group (tg != 0), keep traversing
                         const uint32_t c = SPECN == 1 ? 0u : (oct >> 4) & 3u;
                         pend[(2u * c) * kWave + lane] = tgBase;
                         pend[(2u * c + 1u) * kWave + lane] = tg;
@@ -1885,10 +1916,16 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 PT_DIAG_ADD(sPops, (uint32_t)nL);
                 // up to two primitives of the group per step, both records loaded up front
                 uint32_t k0 = 0u, k1 = 0u;
-                const bool h0 = tg != 0u;
-                if (h0) { k0 = tgBase + (uint32_t)__builtin_ctz(tg); tg &= tg - 1u; }
-                const bool h1 = tg != 0u;
-                if (h1) { k1 = tgBase + (uint32_t)__builtin_ctz(tg); tg &= tg - 1u; }
+                const bool h0 = laneOf(mL);
+                if (h0) k0 = tgBase + (uint32_t)__builtin_ctz(tg);
+                tg &= tg - 1u;   // (every lane: an empty group stays empty)
+                // (tg < 2^24.  The signed compare keeps the ballot a compare of its own: `tg != 0u`
+                // is merged with the `tg - 1u` below into one subtract whose carry-out is the
+                // predicate, and a ballot of that carry rebuilds the mask through a VGPR)
+                const uint64_t m1 = __ballot((int)tg > 0);
+                const bool h1 = laneOf(m1);
+                if (h1) k1 = tgBase + (uint32_t)__builtin_ctz(tg);
+                tg &= tg - 1u;
                 // Every lane loads two records (lanes without a primitive read record 0): a
                 // conditional load would cost a zero fill of 24 registers per step
                 // 32-bit byte offsets off the uniform base (global loads with an SGPR base): no
@@ -1910,9 +1947,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 if (kargs()->S.hasSpheres) {   // (uniform: read where needed)
                     if (h0) wideTest<true>(q0, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
                     if (h1) wideTest<true>(q1, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
-                    const bool s0 = __float_as_uint(q0.p2.w) != 0u, s1 = __float_as_uint(q1.p2.w) != 0u;
-                    sTris += (uint32_t)__popcll(__ballot(h0 && !s0)) + (uint32_t)__popcll(__ballot(h1 && !s1));
-                    sSph += (uint32_t)__popcll(__ballot(h0 && s0)) + (uint32_t)__popcll(__ballot(h1 && s1));
+                    const uint64_t s0 = mL & __ballot(__float_as_uint(q0.p2.w) != 0u);
+                    const uint64_t s1 = m1 & __ballot(__float_as_uint(q1.p2.w) != 0u);
+                    sTris += (uint32_t)nL + (uint32_t)__popcll(m1) - (uint32_t)__popcll(s0) - (uint32_t)__popcll(s1);
+                    sSph += (uint32_t)__popcll(s0) + (uint32_t)__popcll(s1);
                 } else {
                     if constexpr (INST) {
                         if (h0) wideTest<false>(q0, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
@@ -1921,7 +1959,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                         if (h0) wideTestTri(q0, o, d, 0.001f, closest, best, bestLo);
                         if (h1) wideTestTri(q1, o, d, 0.001f, closest, best, bestLo);
                     }
-                    sTris += (uint32_t)__popcll(__ballot(h0)) + (uint32_t)__popcll(__ballot(h1));
+                    sTris += (uint32_t)nL + (uint32_t)__popcll(m1);
                 }
                 if (redo) oct |= 8u;   // order-dependent candidate: repeat the query in the reference's order
                 if (SPEC && tg == 0u && (oct & 48u)) {   // this group is done: the last parked one is next
@@ -1976,15 +2014,17 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         }
         if (kind == 2) {
             // ------------------------------------------------------------------ SHADE
+            const uint64_t shadeM = mS & ~needTaskM;   // lanes whose query is complete
+            const bool shading = laneOf(shadeM);
             if constexpr (WIDE && !INST) {
-                bool redo = wantShade && !needTask && (oct & 8u);
+                bool redo = shading && (oct & 8u);
 #ifdef PT_DIAG
                 bool missed = false;
 #endif
                 // Triangle-only scenes: the reference's leaf-box rule, decided here for the final
                 // hit alone (deferredRedo; bestLo holds t2)
                 if (!kargs()->S.hasSpheres && S.nprims > 1) {
-                    if (wantShade && !needTask && best >= 0 && !redo) {
+                    if (shading && best >= 0 && !redo) {
                         const float4* bx = kargs()->S.wbox + 2 * (size_t)best;
                         redo = deferredRedo(bx[0], *reinterpret_cast<const float2*>(bx + 1), o, inv, closest, bestLo);
 #ifdef PT_DIAG
@@ -2008,10 +2048,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                     best = k >= 0 ? (int)S2.rankOf[k] : -1;
                 }
             }
-            bool newRay = false, newSample = false;
             PT_DIAG_ADD(itS, 1u);
-            if (wantShade && !needTask) {
-                bool done = false;
+            bool done = false;   // the lane's sample is complete
+            if (shading) {
                 float3 contrib = f3(0.0f, 0.0f, 0.0f);
                 if (best < 0) {
                     contrib = PT_SKY();
@@ -2029,60 +2068,54 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                         if (depthLeft == 0) { contrib = PT_SKY(); done = true; }
                     }
                 }
-                if (done) {
-                    sum = add(sum, contrib);
-                    if constexpr (SAMPLE) {
-                        uint4 ts = taskState[lane];
-                        ts.y++;
-                        taskState[lane].y = ts.y;
-                        if (ts.y == ts.z) {
-                            active = false;
-                            PT_FINISH_TASK(ts);
-                        } else {
-                            // A kernarg pointer re-read with no user (kargs' empty asm is volatile):
-                            // without it the sample kernels come out 12 instructions shorter with
-                            // other register assignments, a change to measure before it is made.
-                            (void)kargs();
-                            newSample = true;
-                        }
-                    } else {
-                        ++sample;
-                        if (sample == nSamples) {
-                            active = false;
-                        } else {
-                            newSample = true;
-                        }
-                    }
-                }
-                newRay = true;   // bounce, next sample (newSample) or finished (reset below)
-                if (!active) newRay = false;
+                if (done) sum = add(sum, contrib);
             }
+            // Every lane steps its sample count by `done` (a lane that is not shading by 0; shadeM
+            // masks its stale state): who completed a sample and who its last one comes from two
+            // integer compares, not from predicates joined over the branches above.
+            uint64_t doneM, finM;
+            if constexpr (SAMPLE) {
+                const uint4 ts = taskState[lane];
+                const uint32_t y1 = ts.y + (done ? 1u : 0u);
+                taskState[lane].y = y1;
+                doneM = shadeM & __ballot(y1 != ts.y);
+                finM = doneM & __ballot(y1 == ts.z);
+                if (laneOf(finM)) PT_FINISH_TASK(ts);
+                needTaskM |= finM;
+            } else {
+                const int s1 = sample + (done ? 1 : 0);
+                doneM = shadeM & __ballot(s1 != sample);
+                finM = doneM & __ballot(s1 == nSamples);
+                sample = s1;
+            }
+            activeM &= ~finM;
+            // bounce or next sample (newSampleM) for the lanes that go on
+            uint64_t newRayM = shadeM & ~finM, newSampleM = doneM & ~finM;
 #ifdef PT_DIAG
             const unsigned long long tS1 = __builtin_amdgcn_s_memtime();
 #endif
             if constexpr (SAMPLE) {   // idle lanes take new tasks and start their first path
-                bool got = false;
+                uint64_t got = 0;
                 PT_TAKE_TASKS(got);
-                if (got) {
-                    active = true;
-                    newRay = newSample = true;
-                }
+                activeM |= got;
+                newRayM |= got;
+                newSampleM |= got;
             }
             // one camera-ray and one ray-start site for every lane that needs them
 #ifdef PT_DIAG
             const unsigned long long tS2 = __builtin_amdgcn_s_memtime();
 #endif
-            if (newSample) PT_NEW_PATH();
+            if (laneOf(newSampleM)) PT_NEW_PATH();
 #ifdef PT_DIAG
             const unsigned long long tS3 = __builtin_amdgcn_s_memtime();
 #endif
-            if (newRay) PT_BEGIN_RAY();
+            if (laneOf(newRayM)) PT_BEGIN_RAY();
 #ifdef PT_DIAG
             const unsigned long long tS4 = __builtin_amdgcn_s_memtime();
             cycSh += tS1 - tK0; cycTk += tS2 - tS1; cycNp += tS3 - tS2; cycBr += tS4 - tS3;
 #endif
-            sRays += (uint32_t)__popcll(__ballot(newRay));
-            sPaths += (uint32_t)__popcll(__ballot(newSample));
+            sRays += (uint32_t)__popcll(newRayM);
+            sPaths += (uint32_t)__popcll(newSampleM);
         }
 #ifdef PT_DIAG
         {   // shader-clock cycles per step kind (the step's memory waits included)

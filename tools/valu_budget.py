@@ -15,6 +15,10 @@ grouped into regions: the helper function that contains them, or -- inside rende
 (instructions in the code, once each); the dynamic share of a region is its count times how often
 its code runs (iterations per step kind from a PT_ITER_STATS run, loop trips), which
 DESIGN.md section 11 works out next to this table.
+
+The last column counts lane masks rebuilt through a VGPR inside one basic block (`v_cndmask_b32 v,
+0, 1, mask` followed by `v_cmp_ne_u32 .., 0, v`): what a `__ballot` of a predicate that is no plain
+compare costs (section 11 item 13).
 """
 import collections
 import os
@@ -135,7 +139,7 @@ def main() -> None:
         reg = region.get(line, "?") if f.endswith("pt_device.hip") else os.path.basename(f)
         if reg in GENERIC or line == 0:
             reg = None
-        blk.append((c, reg, (os.path.basename(f), line)))
+        blk.append((c, reg, (os.path.basename(f), line), s))
         if c in ("branch",) and (op.startswith("s_branch") or op.startswith("s_cbranch")):
             blocks.append(blk)
             blk = []
@@ -143,17 +147,28 @@ def main() -> None:
         blocks.append(blk)
     prev = "(no source line)"
     for b in blocks:   # a block of generic code only: the region of the code laid out before it
-        last = next((r for _, r, _ in b if r), prev)
-        for c, r, key in b:
+        last = next((r for _, r, _, _ in b if r), prev)
+        rebuilt = {}   # VGPR written by `v_cndmask 0, 1, mask` -> instructions since
+        for c, r, key, ins in b:
             if r:
                 last = r
             per_region[r or last][c] += 1
             per_line[key][c] += 1
+            # a lane mask rebuilt through a VGPR: v_cndmask_b32 v, 0, 1, s[m] then v_cmp_ne_u32 .., 0, v
+            # (a __ballot of a predicate that is no plain compare; two VALU for a mask that exists)
+            m = re.match(r"v_cndmask_b32_e64 (v\d+), 0, 1, (s\[|vcc)", ins)
+            m2 = re.match(r"v_cmp_ne_u32_e(?:32 vcc|64 s\[\d+:\d+\]), 0, (v\d+)$", ins)
+            rebuilt = {v: n + 1 for v, n in rebuilt.items() if n < 8}
+            if m:
+                rebuilt[m.group(1)] = 0
+            elif m2 and m2.group(1) in rebuilt:
+                per_region[r or last]["rebuild"] += 1
+                del rebuilt[m2.group(1)]
         prev = last
     print(f"kernel {want}: " + ", ".join(f"{k} {v}" for k, v in total.most_common()))
-    print(f"{'region':40s} {'VALU':>6s} {'SALU':>6s} {'VMEM':>5s} {'LDS':>4s} {'br':>4s}")
+    print(f"{'region':40s} {'VALU':>6s} {'SALU':>6s} {'VMEM':>5s} {'LDS':>4s} {'br':>4s} {'mask rebuilds':>14s}")
     for reg, c in sorted(per_region.items(), key=lambda kv: -kv[1]["valu"]):
-        print(f"{reg:40s} {c['valu']:6d} {c['salu']:6d} {c['vmem']:5d} {c['lds']:4d} {c['branch']:4d}")
+        print(f"{reg:40s} {c['valu']:6d} {c['salu']:6d} {c['vmem']:5d} {c['lds']:4d} {c['branch']:4d} {c['rebuild']:14d}")
     print("\ntop source lines by static VALU:")
     src = open(SRC).read().split("\n")
     for (f, line), c in sorted(per_line.items(), key=lambda kv: -kv[1]["valu"])[:45]:
