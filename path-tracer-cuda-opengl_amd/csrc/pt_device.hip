@@ -70,7 +70,9 @@ struct DevScene {
     const float4* shade;     // 3 x float4 per primitive: {n | c, r} {albedo, fuzz} {ir, type | sphere << 16, mat, obj}
     const float4* mats;      // 2 x float4 per material
     const float4* wnodes;    // compressed 8-wide nodes, 5 x float4 each (renderKernelWF<.., WIDE>; host/pt_wide8.cpp)
-    const float4* wprims;    // primitive records in wide-tree leaf order, {v0, rank} {v1, objID} {v2, sphere}
+    const float4* wprims;    // primitive records in wide-tree leaf order, {v0, rank} {v1, objID} {v2, sphere}; the render
+                             // launches of a triangle-only, non-instanced scene get its edge-form records here
+                             // instead, {v0, rank} {v1 - v0, objID} {v2 - v0, 0} (pt_scene::wtris, wideTestTri)
     const float4* wshade;    // shading records in reference rank order (wide kernels)
     const float4* wbox;      // exact triangle boxes in rank order, {mn.x, mx.x, mn.y, mx.y} {mn.z, mx.z, 0, 0} (deferredRedo)
     const uint32_t* rankOf;  // leaf k -> its rank in the reference's traversal order
@@ -457,16 +459,48 @@ __device__ __forceinline__ void wideTest(const Prim& q, float3 o, float3 d, floa
 // exact by construction.  The running `closest` that culls nodes is >= t_M, and the wide planes lie
 // at least 2^emin outside the exact boxes, far beyond the rounding that opens a window [t, lo): M
 // and every candidate inside its window are visited (wideHits).
-__device__ __forceinline__ void wideTestTri(const Prim& q, float3 o, float3 d, float tmin, float& closest, int& best,
-                                            float& t2) {
-    const float t = primHitAny(q, false, o, d, tmin);
-    if (t >= 0.0f) {
-        const int k = (int)__float_as_uint(q.p0.w);
-        const bool better = t < closest || (t == closest && k < best);   // (t == closest: a finite hit, best >= 0)
-        t2 = __builtin_amdgcn_fmed3f(t, closest, t2);
-        closest = better ? t : closest;
-        best = better ? k : best;
-    }
+// q is an edge-form record {v0, rank}{e1, .}{e2, .} (DevScene::wprims of these launches): e1 = v1 -
+// v0 and e2 = v2 - v0 are the subtractions primHitAny starts with, done once per triangle when the
+// tree is built (pt::edgeTriRecords) -- the same bits, six VALU fewer per test.
+//
+// Straight-line code: primHitAny's arithmetic in its written order, then its decisions as lane masks
+// (ballots of plain compares, scalar logic) and three selects.  hasM: the lanes that test a
+// primitive (the others hold record 0 and keep their state).  A candidate is a lane with
+//   det != 0  (NaN passes, as `det == 0` does not reject it),
+//   none of b1 >= 1, b1 <= 0, b2 >= 1, b2 <= 0, b1 + b2 >= 1  (primHitT's tests and NaN reasoning),
+//   t > tmin  (`!(t <= tmin)` and the caller's `t >= 0` in one: tmin > 0, and a NaN fails both forms).
+// det == 0 gives inv = +-inf and infinite or NaN t, b1, b2, which no select lets through.
+// The reciprocal's IEEE-division fallback (pt_math.hpp rcpRN) is the one branch left, taken by the
+// wave when any testing lane needs it.
+__device__ __forceinline__ float rcpRNWave(float x, uint64_t hasM) {
+    if constexpr (!PT_FAST_RCP) return 1.0f / x;
+    const uint32_t ex = (__float_as_uint(x) >> 23) & 0xffu;
+    const uint64_t slowM = hasM & __ballot(ex - kRcpExpLo > kRcpExpHi - kRcpExpLo);
+    float y = rcpNewton(x);
+    if (__builtin_expect(slowM != 0, 0)) y = __builtin_amdgcn_inverse_ballot_w64(slowM) ? 1.0f / x : y;
+    return y;
+}
+__device__ __forceinline__ void wideTestTri(const Prim& q, uint64_t hasM, float3 o, float3 d, float tmin, float& closest,
+                                            int& best, float& t2) {
+    const float3 v0 = xyz(q.p0), e1 = xyz(q.p1), e2 = xyz(q.p2);
+    const float3 s1 = cross3(d, e2);
+    const float det = dot3(s1, e1);
+    const float3 s = sub(o, v0);
+    const float3 s2 = cross3(s, e1);
+    const float inv = rcpRNWave(det, hasM);
+    const float t = dot3(s2, e2) * inv;
+    const float b1 = dot3(s1, s) * inv;
+    const float b2 = dot3(s2, d) * inv;
+    const int k = (int)__float_as_uint(q.p0.w);
+    const uint64_t rejM = __ballot(b1 >= 1.0f) | __ballot(b1 <= 0.0f) | __ballot(b2 >= 1.0f) | __ballot(b2 <= 0.0f) |
+                          __ballot(b1 + b2 >= 1.0f);
+    const uint64_t hitM = hasM & __ballot(det != 0.0f) & __ballot(t > tmin) & ~rejM;
+    // the minimum of (t, ascending rank)  (t == closest: a finite hit, best >= 0)
+    const uint64_t takeM = hitM & (__ballot(t < closest) | (__ballot(t == closest) & __ballot(k < best)));
+    const float mid = __builtin_amdgcn_fmed3f(t, closest, t2);
+    t2 = __builtin_amdgcn_inverse_ballot_w64(hitM) ? mid : t2;
+    closest = __builtin_amdgcn_inverse_ballot_w64(takeM) ? t : closest;
+    best = __builtin_amdgcn_inverse_ballot_w64(takeM) ? k : best;
 }
 // Is the finished query (closest, t2) order-dependent?  xy, z: the best hit's exact box (DevScene::wbox:
 // refLeafBox's planes as {mn, mx} pairs per axis), under refLeafBox's slab arithmetic.
@@ -1533,7 +1567,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 sSph += (uint32_t)__popcll(__ballot(isS_));                                       \
                 if (sph_) wideTest<true>(q_, o, d, inv, 0.001f, closest, best, bestLo, lb_, redo_, 0u); \
                 else if (INST) wideTest<false>(q_, o, d, inv, 0.001f, closest, best, bestLo, lb_, redo_, 0u); \
-                else wideTestTri(q_, o, d, 0.001f, closest, best, bestLo);   /* (SHADE decides) */ \
+                else wideTestTri(q_, __ballot(true), o, d, 0.001f, closest, best, bestLo);   /* (SHADE decides) */ \
             }                                                                                     \
             if ((ng & 0xffu) == 0u) {                                                             \
                 if (sp == 0) break;                                                               \
@@ -1956,8 +1990,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                         if (h0) wideTest<false>(q0, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
                         if (h1) wideTest<false>(q1, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
                     } else {   // the leaf-box rule is decided once, in SHADE (bestLo holds t2)
-                        if (h0) wideTestTri(q0, o, d, 0.001f, closest, best, bestLo);
-                        if (h1) wideTestTri(q1, o, d, 0.001f, closest, best, bestLo);
+                        wideTestTri(q0, mL, o, d, 0.001f, closest, best, bestLo);
+                        wideTestTri(q1, m1, o, d, 0.001f, closest, best, bestLo);
                     }
                     sTris += (uint32_t)nL + (uint32_t)__popcll(m1);
                 }
@@ -3266,6 +3300,8 @@ struct pt_scene {
     DevBuf refitEvents;                     // refit phase 2 input: count, then crossing-node arrivals
     DevBuf wide, wprims, wshade, rankOf;    // compressed 8-wide tree, its primitive and shading records, leaf ranks (PT_KERNEL_WIDE)
     DevBuf wbox;                            // exact primitive boxes in rank order (DevScene::wbox)
+    DevBuf wtris;                           // wprims in edge form (pt::edgeTriRecords): what the render kernels' LEAF step reads
+    bool haveWtris = false;                 // wtris matches wprims (built with the wide tree of a triangle-only scene)
     std::unique_ptr<pt::WideDevBuilder> wideDev;   // device build scratch (PT_BVH_WIDE_DEVICE), kept between builds
     bool wideReady = false;                 // the wide tree matches the current LBVH build
     bool updated = false;                   // pt_scene_update_objects was called: a dynamic scene
@@ -3371,6 +3407,13 @@ int buildWide(pt_scene* s) {
     std::string err;
     if (!pt::buildWide8(prims.data(), boxes.data(), rank.data(), n, w, err)) return fail(PT_ERR_STATE, err);
     int rc;
+    s->haveWtris = !s->hasSpheres;
+    if (s->haveWtris) {
+        std::vector<uint32_t> wtris(w.prims.size());
+        pt::edgeTriRecords(w.prims.data(), n, wtris.data());
+        if ((rc = devReserve(s->wtris, wtris.size() * 4))) return rc;
+        HIP_TRY(hipMemcpy(s->wtris.p, wtris.data(), wtris.size() * 4, hipMemcpyHostToDevice));
+    }
     if ((rc = devReserve(s->wide, w.nodes.size() * 4)) || (rc = devReserve(s->wprims, w.prims.size() * 4)) ||
         (rc = devReserve(s->wshade, wshade.size() * 4)) || (rc = devReserve(s->rankOf, rank.size() * 4)) ||
         (rc = devReserve(s->wbox, wbox.size() * 4)))
@@ -3395,11 +3438,13 @@ int buildWideDevice(pt_scene* s, hipStream_t st) {
         (rc = devReserve(s->wprims, (size_t)n * pt::kW8PrimDwords * 4)) || (rc = devReserve(s->wshade, (size_t)n * 48)) ||
         (rc = devReserve(s->rankOf, (size_t)n * 4)) || (rc = devReserve(s->wbox, (size_t)n * pt::kW8BoxFloats * 4)))
         return rc;
+    s->haveWtris = !s->hasSpheres;
+    if (s->haveWtris && (rc = devReserve(s->wtris, (size_t)n * pt::kW8PrimDwords * 4))) return rc;
     if (!s->wideDev) s->wideDev.reset(new pt::WideDevBuilder);
     pt::WideDevIn in{s->prims.as<float4>(), s->shade.as<float4>(), s->leafBoxes.as<float>(), s->nodes.as<float4>(),
                      s->iparent.as<int>(), s->lparent.as<int>(), s->irange.as<int2>(), n};
     pt::WideDevOut out{s->wide.as<uint32_t>(), s->wprims.as<uint32_t>(), s->wshade.as<float4>(), s->wbox.as<float4>(),
-                       s->rankOf.as<uint32_t>()};
+                       s->rankOf.as<uint32_t>(), s->haveWtris ? s->wtris.as<uint32_t>() : nullptr};
     std::string err;
     const hipError_t e = s->wideDev->build(in, out, st, err);
     if (e != hipSuccess) return fail(err.empty() ? PT_ERR_HIP : PT_ERR_STATE, err.empty() ? hipGetErrorString(e) : err);
@@ -4574,7 +4619,8 @@ int pt_scene_bvh_info(pt_scene* s, int* depth, int64_t* nodes, int64_t* bytes) {
     if (!s->built) return fail(PT_ERR_STATE, "BVH not built");
     if (depth) *depth = s->depth;
     if (nodes) *nodes = s->nobj > 0 ? 2 * s->nobj - 1 : 0;
-    // (+ the wide kernels' exact-box array once the wide tree exists)
+    // (+ the wide kernels' exact-box array once the wide tree exists; like the wide tree's nodes and
+    // its primitive records, the edge-form records of a triangle-only scene are not in this count)
     if (bytes) *bytes = (int64_t)(s->deviceBytes + (s->wideReady && !s->instanced ? (size_t)s->nobj * pt::kW8BoxFloats * 4 : 0));
     return PT_OK;
 }
@@ -4885,6 +4931,8 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     RenderParams P;
     P.S = devScene(s);
     P.S.err = reinterpret_cast<unsigned int*>(f->counters.as<unsigned long long>() + 7);
+    // (the render kernels' triangle-only LEAF path reads edge-form records: DevScene::wprims)
+    if (s->wideReady && s->haveWtris && !s->hasSpheres && !s->instanced) P.S.wprims = s->wtris.as<float4>();
     P.cam.pos = make_float3(cam->origin[0], cam->origin[1], cam->origin[2]);
     P.cam.ll = make_float3(cam->lower_left[0], cam->lower_left[1], cam->lower_left[2]);
     P.cam.hor = make_float3(cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]);

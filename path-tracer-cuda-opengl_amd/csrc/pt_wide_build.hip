@@ -92,6 +92,20 @@ __global__ void shadeByRankKernel(const float4* __restrict__ shade, const float4
     wbox[2 * r + 1] = make_float4(fminf(fminf(a.z, b.z), c.z), fmaxf(fmaxf(a.z, b.z), c.z), 0.0f, 0.0f);
 }
 
+// The wide-order records in edge form, {v0, rank}{v1 - v0, .}{v2 - v0, .}: the arithmetic of
+// pt::edgeTriRecords (one fp32 subtraction per component, denormals kept).
+__global__ void edgeRecordsKernel(const uint4* __restrict__ wprims, int n, uint4* __restrict__ wtris) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint4 a = wprims[3 * (size_t)k], b = wprims[3 * (size_t)k + 1], c = wprims[3 * (size_t)k + 2];
+    const float ax = __uint_as_float(a.x), ay = __uint_as_float(a.y), az = __uint_as_float(a.z);
+    wtris[3 * (size_t)k] = a;
+    wtris[3 * (size_t)k + 1] = make_uint4(__float_as_uint(__uint_as_float(b.x) - ax), __float_as_uint(__uint_as_float(b.y) - ay),
+                                          __float_as_uint(__uint_as_float(b.z) - az), b.w);
+    wtris[3 * (size_t)k + 2] = make_uint4(__float_as_uint(__uint_as_float(c.x) - ax), __float_as_uint(__uint_as_float(c.y) - ay),
+                                          __float_as_uint(__uint_as_float(c.z) - az), c.w);
+}
+
 // ---------------------------------------------------------------------------------- PLOC
 // Node ids: leaf k = k, internal = n + j.  pbox[2 id] = {min xyz, SAH cost}, pbox[2 id + 1] =
 // {max xyz, primitive count | kGroupFlag}; pchild[j] = the two child ids of internal node n + j.
@@ -1589,8 +1603,15 @@ hipError_t WideDevBuilder::build(const WideDevIn& in, WideDevOut& out, hipStream
     const uint32_t* rootCid = static_cast<const uint32_t*>(cid_[cur].p);
 
     // 3. collapse + quantisation, level by level
-    return collapseLevels(n, rootCid, wideDevSlotCap(n) /* <= 2^24: child bases fit the kernels' 24-bit field */, 0u, in.prims,
-                          out.rank, out.nodes, out.wprims, st, err, out.depth, out.slots);
+    WB_TRY(collapseLevels(n, rootCid, wideDevSlotCap(n) /* <= 2^24: child bases fit the kernels' 24-bit field */, 0u, in.prims,
+                          out.rank, out.nodes, out.wprims, st, err, out.depth, out.slots));
+    // 4. the leaf-order records in edge form (triangle-only scenes)
+    if (out.wtris) {
+        edgeRecordsKernel<<<blocks(n, tb), tb, 0, st>>>(reinterpret_cast<const uint4*>(out.wprims), (int)n,
+                                                        reinterpret_cast<uint4*>(out.wtris));
+        WB_TRY(hipGetLastError());
+    }
+    return hipSuccess;
 }
 
 }  // namespace pt

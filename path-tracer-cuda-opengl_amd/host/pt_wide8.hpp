@@ -8,6 +8,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -30,6 +31,27 @@ inline void exactTriBox(const float* rec, float* out) {
         out[2 * a + 1] = std::fmax(std::fmax(rec[a], rec[4 + a]), rec[8 + a]);
     }
     out[6] = out[7] = 0.0f;
+}
+
+// Edge form of n wide-order triangle records {v0, rank}{v1, .}{v2, .} -> {v0, rank}{e1, .}{e2, .}
+// with e1 = v1 - v0, e2 = v2 - v0: the two subtractions every triangle test starts with
+// (cuda_object.h:66-67), done once per triangle instead of once per test.  Each component is one
+// IEEE fp32 subtraction (denormals kept), so a test that starts from the edges computes the same
+// bits.  Word 3 of each 16-B word is copied.  Only triangle-only, non-instanced scenes have the
+// array (DevScene::wprims of their render launches); `out` may not alias `prims`.
+inline void edgeTriRecords(const uint32_t* prims, int64_t n, uint32_t* out) {
+    for (int64_t k = 0; k < n; k++) {
+        const uint32_t* src = prims + (size_t)k * kW8PrimDwords;
+        uint32_t* dst = out + (size_t)k * kW8PrimDwords;
+        float v[kW8PrimDwords];
+        std::memcpy(v, src, sizeof(v));
+        std::memcpy(dst, src, sizeof(v));
+        for (int a = 0; a < 3; a++) {
+            const float e1 = v[4 + a] - v[a], e2 = v[8 + a] - v[a];
+            std::memcpy(dst + 4 + a, &e1, 4);
+            std::memcpy(dst + 8 + a, &e2, 4);
+        }
+    }
 }
 
 // The builders' smallest plane quantum is 2^-kW8EminShift of the larger of the scene's extent and

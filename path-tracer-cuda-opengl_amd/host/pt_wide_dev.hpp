@@ -34,7 +34,8 @@ struct WideDevOut {
     float4* wshade;            // n x 3 float4, shading records in reference rank order
     float4* wbox;              // n x 2 float4, exact triangle boxes in rank order (pt_wide8.hpp exactTriBox)
     uint32_t* rank;            // n: leaf k -> its rank in the reference's traversal order
-    int depth = 0;             // wide levels (root = 1)
+    uint32_t* wtris = nullptr; // n x 12 dwords or null: wprims in edge form (pt_wide8.hpp edgeTriRecords)
+    int depth = 0;            // wide levels (root = 1)
     int64_t slots = 0;         // node slots written
 };
 
