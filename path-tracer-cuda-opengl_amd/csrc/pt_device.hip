@@ -33,6 +33,7 @@
 #include "../host/pt_error.hpp"
 #include "../host/pt_host.hpp"
 #include "../host/pt_inst_dev.hpp"
+#include "../host/pt_instancing.hpp"
 #include "../host/pt_wide8.hpp"
 #include "../host/pt_wide_dev.hpp"
 #include "pt.h"
@@ -3276,11 +3277,11 @@ int stackFor(int depth) {
     return -1;
 }
 
-// A top-level leaf of an instanced scene: an instance entering its mesh's tree at `slot` (the mesh
-// tree's own slot numbering: 0 = its root; relocated with the tree).
-struct InstEntry {
-    uint32_t inst, mesh, slot;
-};
+// The instanced scene's host tree build, mixLimit and wideStackFor: host/pt_instancing.cpp
+using pt::InstEntry;
+using pt::instanceInverse;
+using pt::mixLimit;
+using pt::wideStackFor;
 
 }  // namespace
 
@@ -3454,509 +3455,78 @@ int buildWideDevice(pt_scene* s, hipStream_t st) {
     return PT_OK;
 }
 
-// Instanced scenes: the two-level tree, built on the host -- one 8-wide tree per mesh (binned SAH
-// over the mesh's objects in object space), a top-level 8-wide tree over the instances' world boxes
-// with one instance per leaf, whose leaves become instance records (pt_wide8.hpp), all in one node
-// array: the top level from slot 0, then the meshes' trees.  Shading records in object space, one
-// per mesh primitive (its shading index g); the hit key instance << gBits | g.
-int wideStackFor(int depth);
-struct InstRecCtx {
-    const std::vector<std::array<float, 12>>* minv;
-    const std::vector<uint8_t>* ident;   // 1: identity, 2: translation only, 0: general
-    const std::vector<InstEntry>* entries;
-};
-uint32_t instanceOfRecord(const uint32_t* rec) { return rec[7]; }
-void writeInstanceRecord(uint32_t e, uint32_t* dst, void* ctx) {
-    const InstRecCtx& c = *static_cast<const InstRecCtx*>(ctx);
-    const InstEntry& E = (*c.entries)[e];
-    std::memset(dst, 0, pt::kW8NodeDwords * 4);
-    dst[0] = (*c.ident)[E.inst] == 1 ? 1u : 0u;
-    dst[1] = (*c.ident)[E.inst] == 2 ? 1u : 0u;   // translation only: the kernels move the origin, keep the direction
-    dst[3] = pt::kW8InstanceFlag;
-    dst[4] = E.slot;   // (+ the mesh tree's base slot once the layout is known)
-    dst[5] = E.inst;
-    dst[6] = E.mesh;   // (layout only; cleared with the relocation)
-    std::memcpy(dst + 8, (*c.minv)[E.inst].data(), 48);
+// Instanced scenes: the two-level tree is built on the host (host/pt_instancing.cpp); this is its
+// device half.  What both builds read of the scene (the full build adds the materials and knobs):
+pt::InstancedIn instancedIn(const pt_scene* s) {
+    pt::InstancedIn in{};
+    in.objs = s->objs.data();
+    in.meshFirst = s->meshFirst.data();
+    in.meshCount = s->meshCount.data();
+    in.nMeshes = (int)s->meshFirst.size();
+    in.inst = s->inst.data();
+    in.nInst = (int64_t)s->inst.size();
+    in.nmat = s->nmat;
+    in.dynamic = s->instDynamic;
+    in.farExt = kInstFarExt;
+    return in;
 }
 
-// Partial re-braiding (Benthin et al. 2017): an instance enters its mesh tree below the root, one
-// top-level leaf per internal child of the mesh root, each with its own world box, so the top
-// level separates overlapping instances at the mesh's second level.  The child boxes come from the
-// root's quantised planes (outward-rounded: they contain the subtrees).  Returns the mesh root's
-// internal children {slot, object-space box}; empty when the root has leaf children (then the
-// instance enters at the root).
-struct SubRoot {
-    uint32_t slot;
-    double box[6];
-};
-std::vector<SubRoot> nodeChildren(const pt::Wide8& w, uint32_t slot) {
-    std::vector<SubRoot> out;
-    if (w.nodes.size() < (size_t)(slot + 1) * pt::kW8NodeDwords) return out;
-    const uint32_t* R = w.nodes.data() + (size_t)slot * pt::kW8NodeDwords;
-    float p[3];
-    std::memcpy(p, R, 12);
-    for (int j = 0; j < 8; j++) {
-        const uint32_t mb = (R[6 + (j >> 2)] >> (8 * (j & 3))) & 0xffu;
-        if (mb == 0u) continue;
-        if ((mb & 0xf8u) != 0x38u) return {};   // a leaf child at the root
-        SubRoot sr;
-        sr.slot = R[4] + (mb & 7u);
-        for (int a = 0; a < 3; a++) {
-            const int e = (int)((R[3] >> (8 * a)) & 0xffu) - 127;
-            const uint32_t ql = (R[8 + 4 * a + (j >> 2)] >> (8 * (j & 3))) & 0xffu;
-            const uint32_t qh = (R[10 + 4 * a + (j >> 2)] >> (8 * (j & 3))) & 0xffu;
-            sr.box[a] = (double)p[a] + std::ldexp((double)ql, e);
-            sr.box[3 + a] = (double)p[a] + std::ldexp((double)qh, e);
-        }
-        out.push_back(sr);
-    }
-    return out;
-}
-// The entries `levels` wide levels below the root (a node with leaf children stays an entry).
-void meshSubRoots(const pt::Wide8& w, uint32_t slot, const double* box, int levels, std::vector<SubRoot>& out) {
-    std::vector<SubRoot> ch = levels > 0 ? nodeChildren(w, slot) : std::vector<SubRoot>{};
-    if (ch.empty()) {
-        SubRoot sr;
-        sr.slot = slot;
-        for (int k = 0; k < 6; k++) sr.box[k] = box[k];
-        out.push_back(sr);
-        return;
-    }
-    for (const SubRoot& c : ch) meshSubRoots(w, c.slot, c.box, levels - 1, out);
-}
-
-// Partial re-braiding chosen by surface area (PT_INST_ENTRIES = k > 0): start from the root's
-// internal children and repeatedly open the entry of the largest surface area (a node whose children
-// are all internal) while the entries stay within k per instance -- the large, overlapping boxes are
-// opened, the small ones stay closed (in the spirit of Benthin et al. 2017's SAH-driven re-braiding).
-void meshSubRootsBudget(const pt::Wide8& w, size_t budget, std::vector<SubRoot>& out) {
-    out = nodeChildren(w, 0u);
-    if (out.empty()) return;
-    auto area = [](const SubRoot& r) {
-        const double x = r.box[3] - r.box[0], y = r.box[4] - r.box[1], z = r.box[5] - r.box[2];
-        return x * y + y * z + z * x;
-    };
-    std::vector<bool> closed(out.size(), false);
-    for (;;) {
-        int pick = -1;
-        double best = -1.0;
-        for (size_t i = 0; i < out.size(); i++)
-            if (!closed[i] && area(out[i]) > best) { best = area(out[i]); pick = (int)i; }
-        if (pick < 0) break;
-        std::vector<SubRoot> ch = nodeChildren(w, out[(size_t)pick].slot);
-        if (ch.empty() || out.size() - 1 + ch.size() > budget) { closed[(size_t)pick] = true; continue; }
-        out.erase(out.begin() + pick);
-        closed.erase(closed.begin() + pick);
-        for (const SubRoot& c : ch) { out.push_back(c); closed.push_back(false); }
-    }
-}
-
-float mixLimit(double m);   // (below)
-
-// The world-to-object transform of one instance, in double and rounded to the fp32 rows the
-// kernels read, and its class (1: identity, 2: translation only, 0: general).  False for a singular
-// matrix (|det| <= 1e-30 or not finite).  The one place these are computed: a scene rebuilt after
-// pt_scene_update_instances and a fresh scene of the same matrices carry the same rows bit for bit.
-bool instanceInverse(const pt_instance& I, std::array<float, 12>& minv, std::array<double, 12>& w2o, uint8_t& cls) {
-    const double a[3][3] = {{I.m[0], I.m[1], I.m[2]}, {I.m[4], I.m[5], I.m[6]}, {I.m[8], I.m[9], I.m[10]}};
-    const double t[3] = {I.m[3], I.m[7], I.m[11]};
-    const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
-                       a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
-    if (!(std::fabs(det) > 1e-30) || !std::isfinite(det)) return false;
-    double inv[3][3];
-    inv[0][0] = (a[1][1] * a[2][2] - a[1][2] * a[2][1]) / det;
-    inv[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) / det;
-    inv[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) / det;
-    inv[1][0] = (a[1][2] * a[2][0] - a[1][0] * a[2][2]) / det;
-    inv[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) / det;
-    inv[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) / det;
-    inv[2][0] = (a[1][0] * a[2][1] - a[1][1] * a[2][0]) / det;
-    inv[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) / det;
-    inv[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) / det;
-    bool id = true, lin = true;
-    for (int r = 0; r < 3; r++) {
-        const double it = -(inv[r][0] * t[0] + inv[r][1] * t[1] + inv[r][2] * t[2]);
-        for (int c = 0; c < 3; c++) {
-            minv[(size_t)(4 * r + c)] = (float)inv[r][c];
-            lin = lin && a[r][c] == (r == c ? 1.0 : 0.0);
-        }
-        minv[(size_t)(4 * r + 3)] = (float)it;
-        for (int c = 0; c < 3; c++) w2o[(size_t)(4 * r + c)] = inv[r][c];
-        w2o[(size_t)(4 * r + 3)] = it;
-        id = id && t[r] == 0.0;
-    }
-    id = id && lin;
-    cls = id ? 1 : (lin ? 2 : 0);
-    return true;
-}
-
-// Every instance's transform records: instanceInverse's, and the `winst` entry the kernels read
-// ({world-to-object rows, objBase, class}).
-struct InstRecords {
-    std::vector<std::array<float, 12>> minv;
-    std::vector<uint8_t> ident;   // 1: identity, 2: translation only, 0: general
-    std::vector<float> winst;
-    std::vector<std::array<double, 12>> w2o;   // world-to-object, double
-};
-int instanceRecords(const pt_scene* s, InstRecords& R) {
-    const int64_t ni = (int64_t)s->inst.size();
-    R.minv.resize((size_t)ni);
-    R.ident.assign((size_t)ni, 0);
-    R.winst.assign((size_t)std::max<int64_t>(1, ni) * 16, 0.0f);
-    R.w2o.resize((size_t)ni);
-    uint32_t objBase = 0;
-    for (int64_t i = 0; i < ni; i++) {
-        const pt_instance& I = s->inst[(size_t)i];
-        if (!instanceInverse(I, R.minv[(size_t)i], R.w2o[(size_t)i], R.ident[(size_t)i]))
-            return fail(PT_ERR_INVALID, "instanced scene: instance " + std::to_string(i) + " has a singular transform");
-        for (int k = 0; k < 12; k++) R.winst[(size_t)i * 16 + (size_t)k] = R.minv[(size_t)i][(size_t)k];
-        const uint32_t ob = objBase, idf = R.ident[(size_t)i];   // identity | translation only
-        std::memcpy(&R.winst[(size_t)i * 16 + 12], &ob, 4);
-        std::memcpy(&R.winst[(size_t)i * 16 + 13], &idf, 4);
-        objBase += (uint32_t)s->meshCount[(size_t)I.mesh];
-    }
-    return PT_OK;
-}
-
-// The scene scalars that follow from the world box (its centre and largest extent: instFar's
-// region, camFar; mixLim), and the reach of world ray origins into each mesh's object space.
-// Origins within kInstFarExt world extents of the centre (farther camera rays are moved up to the
-// world box first, renderKernelWF<.., INST>) map into object space within `reach` of the origin; a
-// mesh tree's plane quantum is taken against that reach, not the mesh's own size, so its outward
-// margin (wideHits) holds for every ray that enters it.
-struct InstScalars {
-    float ce[4];   // pt_scene::sceneCE
-    float mixLim;
-};
-void instanceScalars(const pt_scene* s, const double* wmn, const double* wmx, const std::vector<std::array<double, 12>>& w2o,
-                     InstScalars& out, std::vector<double>& reach) {
-    const int64_t ni = (int64_t)s->inst.size();
-    double wext = 0.0, wm = 0.0;
-    for (int a = 0; a < 3; a++) {
-        out.ce[a] = (float)(0.5 * (wmn[a] + wmx[a]));
-        wext = std::max(wext, wmx[a] - wmn[a]);
-        wm = std::max({wm, std::fabs(wmn[a]), std::fabs(wmx[a]), wmx[a] - wmn[a]});
-    }
-    out.ce[3] = std::nextafter((float)wext, INFINITY);
-    out.mixLim = mixLimit(wm);
-    reach.assign(s->meshFirst.size(), 0.0);
-    for (int64_t i = 0; i < ni; i++) {
-        const std::array<double, 12>& W = w2o[(size_t)i];
-        double r = 0.0;
-        for (int c = 0; c < 8; c++) {   // corners of the cube of half-size kInstFarExt world extents (+ 1 %)
-            const double h = 1.01 * kInstFarExt * wext;
-            const double p[3] = {0.5 * (wmn[0] + wmx[0]) + ((c & 1) ? h : -h), 0.5 * (wmn[1] + wmx[1]) + ((c & 2) ? h : -h),
-                                 0.5 * (wmn[2] + wmx[2]) + ((c & 4) ? h : -h)};
-            for (int a = 0; a < 3; a++)
-                r = std::max(r, std::fabs(W[(size_t)(4 * a)] * p[0] + W[(size_t)(4 * a + 1)] * p[1] +
-                                          W[(size_t)(4 * a + 2)] * p[2] + W[(size_t)(4 * a + 3)]));
-        }
-        const int m = s->inst[(size_t)i].mesh;
-        reach[(size_t)m] = std::max(reach[(size_t)m], r);
-    }
-}
-
-// The top level: an 8-wide tree over the entries' world boxes, one entry per leaf, its leaves
-// turned into instance records (the mesh tree's base slot is added by the caller).
-bool instanceTop(const InstRecords& rec, const std::vector<InstEntry>& entries, const float* eboxes, pt::Wide8& top,
-                 std::string& err) {
-    std::vector<uint32_t> iprims(entries.size() * pt::kW8PrimDwords, 0u);
-    for (size_t e = 0; e < entries.size(); e++) iprims[e * pt::kW8PrimDwords + 7] = (uint32_t)e;
-    if (!pt::buildWide8Leaf(iprims.data(), eboxes, nullptr, (int64_t)entries.size(), 1, top, err)) return false;
-    InstRecCtx ctx{&rec.minv, &rec.ident, &entries};
-    return pt::instanceLeaves(top, instanceOfRecord, writeInstanceRecord, &ctx, err);
-}
-// Node slots of a top level over n entries, at most: every node has one block of 8 child slots
-// (internal children and instance records share it) and stands for at least one internal node of
-// the binary tree, of which there are n - 1.
-int64_t instanceTopSlots(int64_t n) { return 1 + 8 * std::max<int64_t>(1, n - 1); }
-
+// The full build: pt::buildInstancedTree on the scene's host copies (the materials come back from
+// the device in the layout the shading records inline), the arrays uploaded, the scene committed.
 int buildInstanced(pt_scene* s) {
     const auto t0 = std::chrono::steady_clock::now();
-    const int nm = (int)s->meshFirst.size();
-    const int64_t ni = (int64_t)s->inst.size();
-    std::vector<pt::Wide8> blas((size_t)nm);
-    std::vector<uint32_t> shade;   // 12 dwords per mesh primitive
-    std::vector<int64_t> meshG0((size_t)nm, 0);
-    int64_t gTotal = 0;
-    int maxDepthB = 0;
-    std::string err;
-    // each mesh's primitive records, boxes and ranks; its tree is built once the instances' reach
-    // into its object space is known (below)
-    std::vector<std::vector<uint32_t>> meshPrims((size_t)nm), meshRank((size_t)nm);
-    std::vector<std::vector<float>> meshBoxes((size_t)nm);
-    for (int m = 0; m < nm; m++) {
-        const int64_t n = s->meshCount[(size_t)m], first = s->meshFirst[(size_t)m];
-        meshG0[(size_t)m] = gTotal;
-        std::vector<uint32_t> prims((size_t)n * pt::kW8PrimDwords, 0u), rank((size_t)n);
-        std::vector<float> boxes((size_t)n * 6);
-        shade.resize((size_t)(gTotal + n) * 12, 0u);
-        std::vector<float4> mats((size_t)std::max<int64_t>(1, 2 * s->nmat));
-        HIP_TRY(hipMemcpy(mats.data(), s->mats.p, mats.size() * sizeof(float4), hipMemcpyDeviceToHost));
-        for (int64_t k = 0; k < n; k++) {
-            const pt_object& o = s->objs[(size_t)(first + k)];
-            uint32_t* r = &prims[(size_t)k * 12];
-            float* f = reinterpret_cast<float*>(r);
-            float* b = &boxes[(size_t)k * 6];
-            uint32_t* sh = &shade[(size_t)(gTotal + k) * 12];
-            float* shf = reinterpret_cast<float*>(sh);
-            r[3] = (uint32_t)o.mat;
-            r[7] = (uint32_t)k;   // the object within its mesh
-            if (o.type == PT_SPHERE) {
-                f[0] = o.v[0]; f[1] = o.v[1]; f[2] = o.v[2]; f[4] = o.v[3]; r[11] = 1u;
-                const float rr = std::fabs(o.v[3]);
-                for (int a = 0; a < 3; a++) { b[a] = o.v[a] - rr; b[3 + a] = o.v[a] + rr; }
-                shf[0] = o.v[0]; shf[1] = o.v[1]; shf[2] = o.v[2]; shf[3] = o.v[3];
-            } else {
-                for (int v = 0; v < 3; v++)
-                    for (int a = 0; a < 3; a++) f[4 * v + a] = o.v[3 * v + a];
-                for (int a = 0; a < 3; a++) {
-                    b[a] = std::fmin(std::fmin(o.v[a], o.v[3 + a]), o.v[6 + a]);
-                    b[3 + a] = std::fmax(std::fmax(o.v[a], o.v[3 + a]), o.v[6 + a]);
-                }
-                // triangle.h:17-19 normalize(cross(v1 - v0, v2 - v0)), the device's operation order
-                const float e1[3] = {o.v[3] - o.v[0], o.v[4] - o.v[1], o.v[5] - o.v[2]};
-                const float e2[3] = {o.v[6] - o.v[0], o.v[7] - o.v[1], o.v[8] - o.v[2]};
-                const float c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-                const float l = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-                if (l != 0.0f) {
-                    const float il = 1.0f / l;
-                    for (int a = 0; a < 3; a++) shf[a] = il * c[a];
-                }
-            }
-            const float4 m0 = mats[(size_t)(2 * o.mat)], m1 = mats[(size_t)(2 * o.mat + 1)];
-            shf[4] = m0.x; shf[5] = m0.y; shf[6] = m0.z; shf[7] = m0.w;
-            uint32_t tp;
-            std::memcpy(&tp, &m1.y, 4);
-            shf[8] = m1.x;
-            sh[9] = tp | (o.type == PT_SPHERE ? 0x10000u : 0u);
-            sh[10] = (uint32_t)o.mat;
-            sh[11] = (uint32_t)k;
-            rank[(size_t)k] = (uint32_t)(gTotal + k);
-        }
-        meshPrims[(size_t)m] = std::move(prims);
-        meshBoxes[(size_t)m] = std::move(boxes);
-        meshRank[(size_t)m] = std::move(rank);
-        gTotal += n;
-    }
-    int gBits = 1;
-    while (((int64_t)1 << gBits) < gTotal) gBits++;
-    if (gBits > 28 || ni > ((int64_t)1 << (30 - gBits)))
-        return fail(PT_ERR_INVALID, "instanced scene: too many instances for the hit key (instance << " +
-                                        std::to_string(gBits) + " | primitive)");
-    // instances: world-to-object transforms, world boxes (every mesh vertex transformed, in double)
-    InstRecords rec;
-    int rc = instanceRecords(s, rec);
-    if (rc) return rc;
-    const std::vector<float>& winst = rec.winst;
-    const std::vector<std::array<double, 12>>& w2o = rec.w2o;
-    std::vector<std::array<double, 6>> ibox((size_t)ni);   // world box of each instance
-    std::vector<uint32_t> used;
-    double wmn[3] = {INFINITY, INFINITY, INFINITY}, wmx[3] = {-INFINITY, -INFINITY, -INFINITY};   // the world box
-    for (int64_t i = 0; i < ni; i++) {
-        const pt_instance& I = s->inst[(size_t)i];
-        const double a[3][3] = {{I.m[0], I.m[1], I.m[2]}, {I.m[4], I.m[5], I.m[6]}, {I.m[8], I.m[9], I.m[10]}};
-        const double t[3] = {I.m[3], I.m[7], I.m[11]};
-        // world box of the instance
-        const int64_t first = s->meshFirst[(size_t)I.mesh], n = s->meshCount[(size_t)I.mesh];
-        if (n == 0) continue;
-        double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-        auto grow = [&](double x, double y, double z) {
-            const double p[3] = {x, y, z};
-            for (int r = 0; r < 3; r++) {
-                const double w = a[r][0] * p[0] + a[r][1] * p[1] + a[r][2] * p[2] + t[r];
-                mn[r] = std::min(mn[r], w);
-                mx[r] = std::max(mx[r], w);
-            }
-        };
-        for (int64_t k = 0; k < n; k++) {
-            const pt_object& o = s->objs[(size_t)(first + k)];
-            if (o.type == PT_SPHERE) {
-                const double rr = std::fabs((double)o.v[3]);
-                for (int c = 0; c < 8; c++)
-                    grow(o.v[0] + ((c & 1) ? rr : -rr), o.v[1] + ((c & 2) ? rr : -rr), o.v[2] + ((c & 4) ? rr : -rr));
-            } else {
-                for (int v = 0; v < 3; v++) grow(o.v[3 * v], o.v[3 * v + 1], o.v[3 * v + 2]);
-            }
-        }
-        for (int r = 0; r < 3; r++) { wmn[r] = std::min(wmn[r], mn[r]); wmx[r] = std::max(wmx[r], mx[r]); }
-        for (int r = 0; r < 3; r++) {
-            ibox[(size_t)i][(size_t)r] = mn[r];
-            ibox[(size_t)i][(size_t)(3 + r)] = mx[r];
-        }
-        used.push_back((uint32_t)i);
-    }
-    if (used.empty()) return fail(PT_ERR_STATE, "instanced scene: no instance of a non-empty mesh");
-    // The scene scalars and each mesh's reach.  A dynamic scene's mesh trees are quantised for twice
-    // the reach, so that ordinary motion stays within it and the later builds keep the trees.
-    std::vector<double> reach;
-    InstScalars sc;
-    instanceScalars(s, wmn, wmx, w2o, sc, reach);
-    for (int a = 0; a < 4; a++) s->sceneCE[a] = sc.ce[a];
-    s->mixLim = sc.mixLim;
-    if (s->instDynamic)
-        for (double& r : reach) r *= 2.0;
-    for (int m = 0; m < nm; m++) {
-        const int64_t n = s->meshCount[(size_t)m];
-        if (n > 0 && !pt::buildWide8(meshPrims[(size_t)m].data(), meshBoxes[(size_t)m].data(), meshRank[(size_t)m].data(),
-                                     n, blas[(size_t)m], err, reach[(size_t)m]))
-            return fail(PT_ERR_STATE, err);
-        maxDepthB = std::max(maxDepthB, blas[(size_t)m].depth);
-    }
-    // top-level leaves: per instance, its mesh root's internal children (re-braided; PT_INST_REBRAID=0:
-    // the mesh root), each with the world box of its object-space box (8 corners in double)
-    const char* rbv = std::getenv("PT_INST_REBRAID");
-    const int rebraid = rbv ? std::max(0, std::min(3, std::atoi(rbv))) : 1;
-    std::vector<std::vector<SubRoot>> sub((size_t)nm);
-    for (int m = 0; m < nm; m++) {
-        const double inf[6] = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
-        const int budget = envCount("PT_INST_ENTRIES", 0);   // (A/B: surface-area-chosen partial re-braiding)
-        if (budget > 0) meshSubRootsBudget(blas[(size_t)m], (size_t)budget, sub[(size_t)m]);
-        else if (rebraid > 0) meshSubRoots(blas[(size_t)m], 0u, inf, rebraid, sub[(size_t)m]);
-        if (sub[(size_t)m].size() == 1) sub[(size_t)m].clear();   // (the root itself)
-    }
-    std::vector<InstEntry> entries;
-    std::vector<float> iboxes;
-    auto addEntry = [&](uint32_t i, uint32_t mesh, uint32_t slot, const double* b) {
-        for (int r = 0; r < 3; r++) iboxes.push_back(std::nextafter((float)b[r], -INFINITY));
-        for (int r = 0; r < 3; r++) iboxes.push_back(std::nextafter((float)b[3 + r], INFINITY));
-        entries.push_back({i, mesh, slot});
-    };
-    for (uint32_t i : used) {
-        const pt_instance& I = s->inst[(size_t)i];
-        const std::vector<SubRoot>& sr = sub[(size_t)I.mesh];
-        if (sr.empty()) {
-            addEntry(i, (uint32_t)I.mesh, 0u, ibox[(size_t)i].data());
-            continue;
-        }
-        for (const SubRoot& r : sr) {
-            double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-            for (int c = 0; c < 8; c++) {
-                const double q[3] = {r.box[(c & 1) ? 3 : 0], r.box[(c & 2) ? 4 : 1], r.box[(c & 4) ? 5 : 2]};
-                for (int a = 0; a < 3; a++) {
-                    const double w = (double)I.m[4 * a] * q[0] + (double)I.m[4 * a + 1] * q[1] + (double)I.m[4 * a + 2] * q[2] +
-                                     (double)I.m[4 * a + 3];
-                    mn[a] = std::min(mn[a], w);
-                    mx[a] = std::max(mx[a], w);
-                }
-            }
-            // (never beyond the instance's exact box)
-            double b[6];
-            for (int a = 0; a < 3; a++) {
-                b[a] = std::max(mn[a], ibox[(size_t)i][(size_t)a]);
-                b[3 + a] = std::min(mx[a], ibox[(size_t)i][(size_t)(3 + a)]);
-            }
-            addEntry(i, (uint32_t)I.mesh, r.slot, b);
-        }
-    }
-    pt::Wide8 top;
-    if (!instanceTop(rec, entries, iboxes.data(), top, err)) return fail(PT_ERR_STATE, err);
-    // layout: the top level from slot 0, then each mesh's tree (child and primitive bases relocated).
-    // A dynamic scene reserves the top level's region at its upper bound for this number of entries
-    // (its slot count changes with the matrices), so that later builds rewrite that region alone.
-    uint32_t topSlots = (uint32_t)(top.nodes.size() / pt::kW8NodeDwords);
-    if (s->instDynamic) {
-        const int64_t cap = instanceTopSlots((int64_t)entries.size());
-        if ((int64_t)topSlots > cap || cap >= ((int64_t)1 << 24))
-            return fail(PT_ERR_STATE, "instanced BVH: top level beyond its reserved node slots");
-        topSlots = (uint32_t)cap;
-        top.nodes.resize((size_t)cap * pt::kW8NodeDwords, 0u);
-    }
-    std::vector<uint32_t> meshRoot((size_t)nm, 0u);
-    uint32_t nodeBase = topSlots, primBase = 0;
-    for (int m = 0; m < nm; m++) {
-        meshRoot[(size_t)m] = nodeBase;
-        pt::relocateWide8(blas[(size_t)m], nodeBase, primBase);
-        nodeBase += (uint32_t)(blas[(size_t)m].nodes.size() / pt::kW8NodeDwords);
-        primBase += (uint32_t)(blas[(size_t)m].prims.size() / pt::kW8PrimDwords);
-    }
-    if ((int64_t)nodeBase >= ((int64_t)1 << 24)) return fail(PT_ERR_STATE, "instanced BVH: more than 2^24 node slots");
-    for (size_t k = 0; k < top.nodes.size(); k += pt::kW8NodeDwords)
-        if (top.nodes[k + 3] == pt::kW8InstanceFlag) {
-            top.nodes[k + 4] += meshRoot[top.nodes[k + 6]];
-            top.nodes[k + 6] = 0u;
-        }
-    std::vector<uint32_t> nodes = top.nodes, prims;
-    for (int m = 0; m < nm; m++) {
-        nodes.insert(nodes.end(), blas[(size_t)m].nodes.begin(), blas[(size_t)m].nodes.end());
-        prims.insert(prims.end(), blas[(size_t)m].prims.begin(), blas[(size_t)m].prims.end());
-    }
-    if (prims.empty()) prims.assign(pt::kW8PrimDwords, 0u);
-    if (shade.empty()) shade.assign(12, 0u);
-    if ((rc = devReserve(s->wide, nodes.size() * 4)) || (rc = devReserve(s->wprims, prims.size() * 4)) ||
-        (rc = devReserve(s->wshade, shade.size() * 4)) || (rc = devReserve(s->winst, winst.size() * 4)))
-        return rc;
-    HIP_TRY(hipMemcpy(s->wide.p, nodes.data(), nodes.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->wprims.p, prims.data(), prims.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->wshade.p, shade.data(), shade.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->winst.p, winst.data(), winst.size() * 4, hipMemcpyHostToDevice));
-    s->gBits = gBits;
-    s->wideDepth = top.depth + 1 + maxDepthB + 1;   // stack: top levels, the marker, the mesh's levels
-    s->wideNodes = (int64_t)(nodes.size() / pt::kW8NodeDwords);
-    s->wideSource = 3;
-    s->wideReady = true;
-    s->deviceBytes = nodes.size() * 4 + prims.size() * 4 + shade.size() * 4 + winst.size() * 4 + (size_t)s->nmat * 32;
     s->instPrepared = false;
+    std::vector<float> mats((size_t)std::max<int64_t>(1, 2 * s->nmat) * 4);
+    HIP_TRY(hipMemcpy(mats.data(), s->mats.p, mats.size() * 4, hipMemcpyDeviceToHost));
+    pt::InstancedIn in = instancedIn(s);
+    in.mats = mats.data();
+    const char* rbv = std::getenv("PT_INST_REBRAID");
+    in.rebraid = rbv ? std::max(0, std::min(3, std::atoi(rbv))) : 1;
+    in.entryBudget = envCount("PT_INST_ENTRIES", 0);
+    pt::InstancedTree t;
+    int rc = pt::buildInstancedTree(in, t);
+    if (rc) return rc;
+    // the buffers and what goes into them (src == nullptr: scratch of the later builds, reserved only)
+    struct Upload { DevBuf* buf; const void* src; size_t bytes; };
+    std::vector<Upload> up = {{&s->wide, t.nodes.data(), t.nodes.size() * 4}, {&s->wprims, t.prims.data(), t.prims.size() * 4},
+                              {&s->wshade, t.shade.data(), t.shade.size() * 4}, {&s->winst, t.winst.data(), t.winst.size() * 4}};
     if (s->instDynamic) {   // what the later builds need (rebuildInstancedTop)
-        std::vector<pt::InstBoxDesc> desc((size_t)ni);
-        std::vector<int32_t> subFirst((size_t)nm, -1);
-        std::vector<double> subBoxes;
-        for (int m = 0; m < nm; m++) {
-            if (sub[(size_t)m].empty()) continue;
-            subFirst[(size_t)m] = (int32_t)(subBoxes.size() / 6);
-            for (const SubRoot& r : sub[(size_t)m]) subBoxes.insert(subBoxes.end(), r.box, r.box + 6);
-        }
-        size_t e = 0;
-        for (int64_t i = 0; i < ni; i++) {
-            const int mesh = s->inst[(size_t)i].mesh;
-            pt::InstBoxDesc& D = desc[(size_t)i];
-            D = pt::InstBoxDesc{};
-            D.objFirst = (int32_t)s->meshFirst[(size_t)mesh];
-            D.objCount = (int32_t)s->meshCount[(size_t)mesh];
-            D.entryFirst = (int32_t)e;
-            D.subFirst = subFirst[(size_t)mesh];
-            D.entryCount = D.objCount == 0 ? 0 : (D.subFirst < 0 ? 1 : (int32_t)sub[(size_t)mesh].size());
-            e += (size_t)D.entryCount;
-        }
-        if (e != entries.size()) return fail(PT_ERR_STATE, "instanced BVH: entry count mismatch");
-        if (subBoxes.empty()) subBoxes.assign(6, 0.0);
-        const size_t outBytes = (size_t)ni * 48 + entries.size() * 24;
-        if ((rc = devReserve(s->instM, (size_t)ni * 48)) || (rc = devReserve(s->instDesc, desc.size() * sizeof(pt::InstBoxDesc))) ||
-            (rc = devReserve(s->instSub, subBoxes.size() * 8)) || (rc = devReserve(s->instOut, outBytes)))
-            return rc;
-        HIP_TRY(hipMemcpy(s->instDesc.p, desc.data(), desc.size() * sizeof(pt::InstBoxDesc), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->instSub.p, subBoxes.data(), subBoxes.size() * 8, hipMemcpyHostToDevice));
-        const size_t ne = entries.size();
-        std::vector<uint32_t> eprims(ne * pt::kW8PrimDwords, 0u), erank(ne), eflat(ne * 3), eroot((size_t)std::max(1, nm), 0u);
-        for (size_t k = 0; k < ne; k++) {
-            eprims[k * pt::kW8PrimDwords + 7] = (uint32_t)k;
-            erank[k] = (uint32_t)k;
-            eflat[3 * k] = entries[k].inst; eflat[3 * k + 1] = entries[k].mesh; eflat[3 * k + 2] = entries[k].slot;
-        }
-        for (int m = 0; m < nm; m++) eroot[(size_t)m] = meshRoot[(size_t)m];
-        if ((rc = devReserve(s->instPrims, eprims.size() * 4)) || (rc = devReserve(s->instRank, erank.size() * 4)) ||
-            (rc = devReserve(s->instEntriesDev, eflat.size() * 4)) || (rc = devReserve(s->instMeshRootDev, eroot.size() * 4)) ||
-            (rc = devReserve(s->instWprims, eprims.size() * 4)) || (rc = devReserve(s->instErr, 16)))
-            return rc;
-        HIP_TRY(hipMemcpy(s->instPrims.p, eprims.data(), eprims.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->instRank.p, erank.data(), erank.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->instEntriesDev.p, eflat.data(), eflat.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->instMeshRootDev.p, eroot.data(), eroot.size() * 4, hipMemcpyHostToDevice));
+        const size_t ni = s->inst.size(), ne = t.entries.size();
+        up.insert(up.end(), {{&s->instM, nullptr, ni * 48}, {&s->instOut, nullptr, ni * 48 + ne * 24},
+                             {&s->instDesc, t.desc.data(), t.desc.size() * sizeof(pt::InstBoxDesc)},
+                             {&s->instSub, t.subBoxes.data(), t.subBoxes.size() * 8},
+                             {&s->instPrims, t.entryPrims.data(), t.entryPrims.size() * 4}, {&s->instWprims, nullptr, t.entryPrims.size() * 4},
+                             {&s->instRank, t.entryRank.data(), t.entryRank.size() * 4}, {&s->instEntriesDev, t.entries.data(), ne * sizeof(InstEntry)},
+                             {&s->instMeshRootDev, t.meshRoot.data(), t.meshRoot.size() * 4}});
+        if ((rc = devReserve(s->instErr, 16))) return rc;
         if (!s->wideDev) s->wideDev.reset(new pt::WideDevBuilder);
         HIP_TRY(s->wideDev->reserveTop((int64_t)ne));   // the later builds allocate nothing
-        s->instReach = reach;
-        s->instEntries = entries;
-        s->instMeshRoot = meshRoot;
-        s->instTopCap = topSlots;
-        s->instMaxDepthB = maxDepthB;
-        s->deviceBytes += (size_t)ni * 48 + desc.size() * sizeof(pt::InstBoxDesc) + subBoxes.size() * 8 + outBytes +
-                          2 * eprims.size() * 4 + erank.size() * 4 + eflat.size() * 4 + eroot.size() * 4;
+    }
+    size_t bytes = (size_t)s->nmat * 32;
+    for (const Upload& u : up) {
+        if ((rc = devReserve(*u.buf, u.bytes))) return rc;
+        if (u.src) HIP_TRY(hipMemcpy(u.buf->p, u.src, u.bytes, hipMemcpyHostToDevice));
+        bytes += u.bytes;
+    }
+    std::copy(t.sceneCE, t.sceneCE + 4, s->sceneCE);
+    s->mixLim = t.mixLim;
+    s->gBits = t.gBits;
+    s->wideDepth = t.depth;
+    s->wideNodes = (int64_t)(t.nodes.size() / pt::kW8NodeDwords);
+    s->wideSource = 3;
+    s->wideReady = true;
+    s->deviceBytes = bytes;
+    if (s->instDynamic) {
+        s->instReach = std::move(t.reach);
+        s->instEntries = std::move(t.entries);
+        s->instMeshRoot = std::move(t.meshRoot);
+        s->instTopCap = t.topCap;
+        s->instMaxDepthB = t.maxDepthB;
         s->instPrepared = true;
     }
     s->wideBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     s->buildMs = s->wideBuildMs;
     s->depth = 0;
-    if (wideStackFor(s->wideDepth) < 0) return fail(PT_ERR_STATE, "instanced BVH too deep");
     s->built = true;
     return PT_OK;
 }
@@ -3978,8 +3548,9 @@ int rebuildInstancedTop(pt_scene* s, hipStream_t st, bool* done) {
     *done = false;
     const int64_t ni = (int64_t)s->inst.size();
     const size_t ne = s->instEntries.size();
-    InstRecords rec;
-    int rc = instanceRecords(s, rec);
+    const pt::InstancedIn scn = instancedIn(s);
+    pt::InstRecords rec;
+    int rc = pt::instanceRecords(scn, rec);
     if (rc) return rc;
     std::vector<float>& hm = s->instHostM;
     std::vector<double>& ibox = s->instHostBox;
@@ -4009,9 +3580,9 @@ int rebuildInstancedTop(pt_scene* s, hipStream_t st, bool* done) {
             wmx[r] = std::max(wmx[r], ibox[(size_t)i * 6 + 3 + (size_t)r]);
         }
     }
-    InstScalars sc;
+    pt::InstScalars sc;
     std::vector<double> reach;
-    instanceScalars(s, wmn, wmx, rec.w2o, sc, reach);
+    pt::instanceScalars(scn, wmn, wmx, rec.w2o, sc, reach);
     for (size_t m = 0; m < reach.size(); m++)
         if (!(reach[m] <= s->instReach[m])) {
             guard.ok = true;
@@ -4051,13 +3622,6 @@ int rebuildInstancedTop(pt_scene* s, hipStream_t st, bool* done) {
     s->built = true;
     *done = true;
     return PT_OK;
-}
-
-// Traversal stack entries of the wide kernels (one dword per entry): >= the tree depth.
-int wideStackFor(int depth) {
-    for (int st : {8, 16, 24})
-        if (depth <= st) return st;
-    return -1;
 }
 
 int setDevice(int dev) {
@@ -4192,21 +3756,6 @@ int filmInit(pt_film* f, hipStream_t st) {
                                                                  f->stripe_h, f->nparts, f->part);
     HIP_TRY(hipGetLastError());
     return PT_OK;
-}
-
-// DevScene::mixLim for a scene whose coordinates and extent are at most m.  Both wide builders
-// (host/pt_wide8.cpp, csrc/pt_wide_build.hip) give a node the plane quantum s = 2^e with e the
-// larger of ceil(log2(m)) - 18 and ceil(log2(node extent / 251)), so s <= 2^eS with
-// eS = ceil(log2(m)) + 1; then |s * 2^24 * inv| < 2^128 (finite) for |inv| <= 2^(103 - eS), and the
-// exponent byte + 24 stays below 255 for eS <= 100.  Beyond that, every ray takes the reference order.
-float mixLimit(double m) {
-    if (!(m > 0.0) || !std::isfinite(m)) return m == 0.0 ? FLT_MAX : -1.0f;
-    int ex = 0;
-    const double f = std::frexp(m, &ex);   // m = f * 2^ex, f in [0.5, 1): ceil(log2(m)) = ex, or ex - 1 at f = 0.5
-    const int eS = (f == 0.5 ? ex - 1 : ex) + 1;
-    if (eS > 100) return -1.0f;
-    if (103 - eS >= 127) return FLT_MAX;
-    return std::ldexp(1.0f, 103 - eS);
 }
 
 DevScene devScene(const pt_scene* s) {

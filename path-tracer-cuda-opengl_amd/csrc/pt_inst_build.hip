@@ -5,7 +5,7 @@
 // componentwise min / max; the partial boxes are reduced by wave shuffles, then across the
 // workgroup's waves through LDS.  min and max are exact and order-free, and each transformed
 // coordinate is the host's expression a0 * x + a1 * y + a2 * z + t evaluated left to right without
-// contraction, so the box is the one buildInstanced computes.  The same workgroup then writes the
+// contraction, so the box is the one buildInstancedTree computes.  The same workgroup then writes the
 // instance's top-level entries: each sub-root's object-space box taken through the matrix (eight
 // corners), clipped to the instance's exact box and rounded to float outward.
 // One workgroup per instance whatever its mesh's size: the scenes this serves have many instances

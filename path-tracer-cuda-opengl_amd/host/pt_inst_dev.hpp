@@ -5,26 +5,17 @@
 // two-level tree stay as they are; what changes with the matrices is small except for one part: the
 // exact world box of every instance, which takes every vertex of its mesh through the matrix in
 // fp64 (C5-instanced: 3.1 M vertex transforms).  That part, and the world boxes of the top-level
-// entries derived from it, are computed here, in the host's operation order (buildInstanced,
-// pt_device.hip; -ffp-contract=off on both sides), so the boxes equal the host's bit for bit.
+// entries derived from it, are computed here, in the host's operation order (buildInstancedTree,
+// host/pt_instancing.cpp; -ffp-contract=off on both sides), so the boxes equal the host's bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "pt.h"
+#include "pt_instancing.hpp"   // InstBoxDesc: one instance's objects and top-level entries
 
 namespace pt {
-
-// One instance: its mesh's objects, and its top-level entries.  An entry is the instance entering
-// its mesh tree at a re-braided sub-root; subFirst < 0: a single entry at the mesh root, whose box
-// is the instance's exact box.  entryCount == 0: an instance of an empty mesh (no box, no entry).
-struct InstBoxDesc {
-    int32_t objFirst, objCount;
-    int32_t entryFirst, entryCount;
-    int32_t subFirst;
-    int32_t pad[3];
-};
 
 struct InstBoxIn {
     const pt_object* objs;     // the scene's objects (object space)

@@ -367,7 +367,7 @@ bool buildWide8Leaf(const uint32_t* prims, const float* boxes, const uint32_t* r
     // the centre -- farther ones are traced in the reference's order, pt_device.hip wideFar):
     // 2^-18 of the larger of the scene's extent and coordinates -- or of `scaleFloor` when that is
     // larger: an instanced mesh's rays arrive in its object space from the whole world
-    // (pt_device.hip buildInstanced), so its planes keep the margin for those origins.
+    // (pt_instancing.cpp buildInstancedTree), so its planes keep the margin for those origins.
     double ext = std::isfinite(scaleFloor) && scaleFloor > 0.0 ? scaleFloor : 0.0;
     for (int a = 0; a < 3; a++)
         ext = std::max({ext, std::fabs((double)rootBox.mn[a]), std::fabs((double)rootBox.mx[a]),

@@ -12,6 +12,8 @@
 #include <string>
 #include <vector>
 
+#include "pt.h"
+
 namespace pt {
 
 #ifndef PT_NODE_DWORDS
@@ -31,6 +33,30 @@ inline void exactTriBox(const float* rec, float* out) {
         out[2 * a + 1] = std::fmax(std::fmax(rec[a], rec[4 + a]), rec[8 + a]);
     }
     out[6] = out[7] = 0.0f;
+}
+
+// The 48-byte primitive record of an object, {v0, mat}{v1, id}{v2, 0} or {c, mat}{r, 0, 0, id}{0, 0, 0, 1},
+// and its box {min xyz, max xyz}, as the LBVH's leafGatherKernel writes them (pt_device.hip): the
+// input of buildWide8.  id: what the caller numbers the object by (the scene's object id, or the
+// object within its mesh).
+inline void primRecord(const pt_object& o, uint32_t id, uint32_t* rec, float* box) {
+    float f[kW8PrimDwords] = {};
+    if (o.type == PT_SPHERE) {
+        f[0] = o.v[0]; f[1] = o.v[1]; f[2] = o.v[2]; f[4] = o.v[3];
+        const float rr = std::fabs(o.v[3]);
+        for (int a = 0; a < 3; a++) { box[a] = o.v[a] - rr; box[3 + a] = o.v[a] + rr; }
+    } else {
+        for (int v = 0; v < 3; v++)
+            for (int a = 0; a < 3; a++) f[4 * v + a] = o.v[3 * v + a];
+        for (int a = 0; a < 3; a++) {
+            box[a] = std::fmin(std::fmin(o.v[a], o.v[3 + a]), o.v[6 + a]);
+            box[3 + a] = std::fmax(std::fmax(o.v[a], o.v[3 + a]), o.v[6 + a]);
+        }
+    }
+    std::memcpy(rec, f, sizeof(f));
+    rec[3] = (uint32_t)o.mat;
+    rec[7] = id;
+    rec[11] = o.type == PT_SPHERE ? 1u : 0u;
 }
 
 // Edge form of n wide-order triangle records {v0, rank}{v1, .}{v2, .} -> {v0, rank}{e1, .}{e2, .}

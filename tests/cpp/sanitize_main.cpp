@@ -1,7 +1,9 @@
 // Sanitizer driver (TEST INFRASTRUCTURE: compiled and run by tests/test_sanitizers.py with
 // -fsanitize=address,undefined and, separately, -fsanitize=thread; the product never uses it).
 // Exercises the host code of libpt (host/pt_host.cpp: scene presets, OBJ loading, Morton keys,
-// quantisation, PNG writing; host/pt_wide8.cpp: the 16-thread binned-SAH wide build) and the CPU
+// quantisation, PNG writing; host/pt_wide8.cpp: the 16-thread binned-SAH wide build;
+// host/pt_instancing.cpp: an instanced scene's two-level tree, from the inst_*.bin files the test
+// writes into out_dir) and the CPU
 // restatement (oracle/pt_oracle.cpp: LBVH, closest hits, threaded compat and sample-mode renders)
 // on the BASELINE scenes at small frame sizes.  SURVEY §5 asks for ASan/UBSan on the CPU build and
 // TSan on its threaded code.  usage: sanitize_main models_dir out_dir [light]
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "pt.h"
+#include "pt_instancing.hpp"
 #include "pt_oracle.h"
 #include "pt_wide8.hpp"
 
@@ -31,23 +34,7 @@ void wideBuild(const pt_object* objs, int64_t n, const std::vector<uint64_t>& ke
     std::vector<float> boxes((size_t)n * 6);
     for (int64_t k = 0; k < n; k++) {
         const pt_object& o = objs[keys[(size_t)k] & 0xffffffffu];
-        uint32_t* r = &prims[(size_t)k * 12];
-        float* f = reinterpret_cast<float*>(r);
-        float* b = &boxes[(size_t)k * 6];
-        r[3] = (uint32_t)o.mat;
-        r[7] = (uint32_t)(keys[(size_t)k] & 0xffffffffu);
-        if (o.type == PT_SPHERE) {
-            f[0] = o.v[0]; f[1] = o.v[1]; f[2] = o.v[2]; f[4] = o.v[3]; r[11] = 1u;
-            const float rr = std::fabs(o.v[3]);
-            for (int a = 0; a < 3; a++) { b[a] = o.v[a] - rr; b[3 + a] = o.v[a] + rr; }
-        } else {
-            for (int v = 0; v < 3; v++)
-                for (int a = 0; a < 3; a++) f[4 * v + a] = o.v[3 * v + a];
-            for (int a = 0; a < 3; a++) {
-                b[a] = std::fmin(std::fmin(o.v[a], o.v[3 + a]), o.v[6 + a]);
-                b[3 + a] = std::fmax(std::fmax(o.v[a], o.v[3 + a]), o.v[6 + a]);
-            }
-        }
+        pt::primRecord(o, (uint32_t)(keys[(size_t)k] & 0xffffffffu), &prims[(size_t)k * 12], &boxes[(size_t)k * 6]);
     }
     std::vector<uint32_t> lref((size_t)(n > 1 ? n - 1 : 1)), rref(lref.size());
     for (int64_t i = 0; i + 1 < n; i++) {
@@ -60,6 +47,47 @@ void wideBuild(const pt_object* objs, int64_t n, const std::vector<uint64_t>& ke
     std::string err;
     check(pt::buildWide8(prims.data(), boxes.data(), rank.data(), n, w, err), "buildWide8");
     check(w.depth > 0 && w.usedNodes > 0, "wide tree non-empty");
+}
+
+template <class T>
+std::vector<T> readAll(const std::string& path) {
+    std::vector<T> v;
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) return v;
+    std::fseek(f, 0, SEEK_END);
+    const long n = std::ftell(f);
+    std::fseek(f, 0, SEEK_SET);
+    v.resize((size_t)n / sizeof(T));
+    if (n > 0 && std::fread(v.data(), 1, (size_t)n, f) != (size_t)n) v.clear();
+    std::fclose(f);
+    return v;
+}
+
+// The instanced build (one wide build per mesh, the top level, the layout for instance updates) of
+// the scene in dir/inst_{objs,meshes,inst,mats}.bin (tests/helpers.py write_instanced_scene).
+void instancedTree(const std::string& dir) {
+    const std::vector<pt_object> objs = readAll<pt_object>(dir + "/inst_objs.bin");
+    const std::vector<int64_t> meshes = readAll<int64_t>(dir + "/inst_meshes.bin");   // the firsts, then the counts
+    const std::vector<pt_instance> inst = readAll<pt_instance>(dir + "/inst_inst.bin");
+    const std::vector<float> mats = readAll<float>(dir + "/inst_mats.bin");
+    check(!objs.empty() && !meshes.empty() && !inst.empty() && !mats.empty(), "instanced scene files");
+    if (failures) return;
+    pt::InstancedIn in{};
+    in.objs = objs.data();
+    in.nMeshes = (int)(meshes.size() / 2);
+    in.meshFirst = meshes.data();
+    in.meshCount = meshes.data() + in.nMeshes;
+    in.inst = inst.data();
+    in.nInst = (int64_t)inst.size();
+    in.mats = mats.data();
+    in.nmat = (int64_t)(mats.size() / 8);
+    in.dynamic = true;
+    in.rebraid = 1;
+    in.farExt = 2.0f;
+    pt::InstancedTree t;
+    check(pt::buildInstancedTree(in, t) == PT_OK, "buildInstancedTree");
+    check(!t.entries.empty() && t.desc.size() == inst.size() && t.nodes.size() > (size_t)t.topCap * pt::kW8NodeDwords,
+          "instanced tree non-empty, laid out for updates");
 }
 
 void scene(const char* name, const char* models, const std::string& outDir, bool light) {
@@ -126,6 +154,7 @@ int main(int argc, char** argv) {
     for (const char* name : {"rtiow", "triangle_world", "random_world", "test_world", "cornell", "bunny_cornell"})
         scene(name, models, out, light);
     if (!light) scene("bunny_field", models, out, light);
+    instancedTree(out);
     // OBJ loading and camera movement (host surface)
     pt_object* objs = nullptr;
     int64_t count = 0;

@@ -192,23 +192,7 @@ int main(int argc, char** argv) {
     std::vector<float> boxes((size_t)n * 6);
     for (int64_t k = 0; k < n; k++) {
         const pt_object& o = objs[keys[k] & 0xffffffffu];
-        uint32_t* r = &prims[(size_t)k * 12];
-        float* f = reinterpret_cast<float*>(r);
-        float* b = &boxes[(size_t)k * 6];
-        r[3] = (uint32_t)o.mat;
-        r[7] = (uint32_t)(keys[k] & 0xffffffffu);
-        if (o.type == PT_SPHERE) {
-            f[0] = o.v[0]; f[1] = o.v[1]; f[2] = o.v[2]; f[4] = o.v[3]; r[11] = 1u;
-            const float rr = std::fabs(o.v[3]);
-            for (int a = 0; a < 3; a++) { b[a] = o.v[a] - rr; b[3 + a] = o.v[a] + rr; }
-        } else {
-            for (int v = 0; v < 3; v++)
-                for (int a = 0; a < 3; a++) f[4 * v + a] = o.v[3 * v + a];
-            for (int a = 0; a < 3; a++) {
-                b[a] = std::fmin(std::fmin(o.v[a], o.v[3 + a]), o.v[6 + a]);
-                b[3 + a] = std::fmax(std::fmax(o.v[a], o.v[3 + a]), o.v[6 + a]);
-            }
-        }
+        pt::primRecord(o, (uint32_t)(keys[k] & 0xffffffffu), &prims[(size_t)k * 12], &boxes[(size_t)k * 6]);
     }
     // reference ranks from the binary tree's child refs (leaf bit 31, leaf k in the low bits)
     std::vector<uint32_t> lref((size_t)std::max<int64_t>(1, n - 1)), rref(lref.size());

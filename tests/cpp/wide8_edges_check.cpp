@@ -96,17 +96,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "triangle-only scenes have edge records; object %lld is a sphere\n", (long long)k);
             return 2;
         }
-        uint32_t* r = &prims[(size_t)k * 12];
-        float* f = reinterpret_cast<float*>(r);
-        float* b = &boxes[(size_t)k * 6];
-        r[3] = (uint32_t)o.mat;
-        r[7] = (uint32_t)(keys[k] & 0xffffffffu);
-        for (int v = 0; v < 3; v++)
-            for (int a = 0; a < 3; a++) f[4 * v + a] = o.v[3 * v + a];
-        for (int a = 0; a < 3; a++) {
-            b[a] = std::fmin(std::fmin(o.v[a], o.v[3 + a]), o.v[6 + a]);
-            b[3 + a] = std::fmax(std::fmax(o.v[a], o.v[3 + a]), o.v[6 + a]);
-        }
+        pt::primRecord(o, (uint32_t)(keys[k] & 0xffffffffu), &prims[(size_t)k * 12], &boxes[(size_t)k * 6]);
     }
     std::vector<uint32_t> lref((size_t)std::max<int64_t>(1, n - 1)), rref(lref.size());
     for (int64_t i = 0; i + 1 < n; i++) {

@@ -1,4 +1,5 @@
 """Scene / ray generators shared by the CPU and GPU test modules (seeded, deterministic)."""
+import os
 import struct
 import zlib
 
@@ -6,6 +7,7 @@ import numpy as np
 
 OBJECT_DTYPE = np.dtype([("type", "<i4"), ("mat", "<i4"), ("v", "<f4", (9,))])
 MATERIAL_DTYPE = np.dtype([("type", "<i4"), ("albedo", "<f4", (3,)), ("fuzz", "<f4"), ("ir", "<f4")])
+INSTANCE_DTYPE = np.dtype([("m", "<f4", (12,)), ("mesh", "<i4"), ("reserved", "<i4")])   # pt_instance
 
 
 def random_soup(n_tri: int, n_sph: int, seed: int, spread: float = 10.0, n_mat: int = 4):
@@ -30,6 +32,64 @@ def random_soup(n_tri: int, n_sph: int, seed: int, spread: float = 10.0, n_mat: 
         mats[m]["fuzz"] = 0.3 if t == 2 else 0.0
         mats[m]["ir"] = 1.5 if t == 4 else 0.0
     return objs, mats
+
+
+def random_transforms(n, seed, reach=30.0):
+    """Rotations with uniform scales in [0.5, 2] and translations in +-reach.  Proper rotations only
+    (LAPACK's QR of a 3 x 3 matrix returns det Q = +1): mirrors, stretches and shears live in
+    test_gpu_instance_affine.py."""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((n, 12), np.float32)
+    for i in range(n):
+        q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+        s = rng.uniform(0.5, 2.0)
+        out[i] = np.concatenate([q * s, rng.uniform(-reach, reach, (3, 1))], 1).reshape(-1)
+    return out
+
+
+def two_triangles():
+    """A mesh whose wide root has leaf children: its instances enter at the root."""
+    tri = np.zeros(2, OBJECT_DTYPE)
+    tri["type"] = 3
+    tri["v"][0] = [-2, -2, 0, 2, -2, 0, 2, 2, 0.5]
+    tri["v"][1] = [-2, -2, 0, 2, 2, 0.5, -2, 2, 0]
+    return tri
+
+
+def tree_shape_instances(count, seed):
+    """test_tree_shapes' instances (tests/test_gpu_instance_update.py) of the meshes {two triangles,
+    a soup, an empty mesh}: count of the first two in turn, one of the empty mesh among them.
+    Returns (matrices, mesh indices, the translations' reach)."""
+    reach = 30.0 * np.cbrt(count / 40.0)
+    mesh = np.insert(np.arange(count) % 2, count // 2, 2)
+    return random_transforms(count + 1, seed, reach), mesh, reach
+
+
+def tree_shape_meshes():
+    """The meshes of the CPU instancing tests: two triangles, a small soup, an empty mesh; and the
+    soup's materials."""
+    soup, mats = random_soup(60, 6, seed=21, spread=4.0)
+    return [two_triangles(), soup, np.zeros(0, OBJECT_DTYPE)], mats
+
+
+def write_instanced_scene(directory, meshes, mats, m, mesh):
+    """The input files of tests/cpp/inst_build_check.cpp (and sanitize_main.cpp's instanced section):
+    objects, mesh ranges {firsts, counts}, pt_instance records, and the materials as 8 floats each,
+    the layout pt_scene_create writes: {albedo, fuzz}, {ir, type bits, 0, 0}.  Returns the paths."""
+    count = np.array([len(p) for p in meshes], np.int64)
+    first = np.concatenate([[0], np.cumsum(count)[:-1]]).astype(np.int64)
+    inst = np.zeros(len(m), INSTANCE_DTYPE)
+    inst["m"] = m
+    inst["mesh"] = mesh
+    dm = np.zeros((len(mats), 8), np.float32)
+    dm[:, 0:3] = mats["albedo"]
+    dm[:, 3] = mats["fuzz"]
+    dm[:, 4] = mats["ir"]
+    dm[:, 5] = mats["type"].astype(np.uint32).view(np.float32)
+    paths = [os.path.join(str(directory), n) for n in ("inst_objs.bin", "inst_meshes.bin", "inst_inst.bin", "inst_mats.bin")]
+    for path, a in zip(paths, (np.concatenate(meshes), np.concatenate([first, count]), inst, dm)):
+        a.tofile(path)
+    return paths
 
 
 def duplicate_centroids(n: int):

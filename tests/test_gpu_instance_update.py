@@ -13,22 +13,9 @@ import numpy as np
 import pytest
 import torch  # noqa: F401  before libpt.so loads (the two must share torch's HIP runtime)
 
-from helpers import OBJECT_DTYPE, random_rays, random_soup, rays_to_struct
+from helpers import OBJECT_DTYPE, random_rays, random_soup, random_transforms, rays_to_struct
 
 pytestmark = pytest.mark.gpu
-
-
-def random_transforms(n, seed, reach=30.0):
-    """Rotations with uniform scales in [0.5, 2] and translations in +-reach.  Proper rotations only
-    (LAPACK's QR of a 3 x 3 matrix returns det Q = +1): mirrors, stretches and shears live in
-    test_gpu_instance_affine.py."""
-    rng = np.random.default_rng(seed)
-    out = np.zeros((n, 12), np.float32)
-    for i in range(n):
-        q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
-        s = rng.uniform(0.5, 2.0)
-        out[i] = np.concatenate([q * s, rng.uniform(-reach, reach, (3, 1))], 1).reshape(-1)
-    return out
 
 
 def flatten(objects, mesh_first, mesh_count, instances):

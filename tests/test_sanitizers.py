@@ -1,9 +1,9 @@
 """CPU sanitizer runs (ASan/UBSan on the CPU build, TSan on its threaded code).
 
 tests/cpp/sanitize_main.cpp drives libpt's host code (host/pt_host.cpp, host/pt_wide8.cpp with its
-16-thread build) and the CPU restatement (oracle/pt_oracle.cpp, threaded renders) over every
-BASELINE scene; it is compiled from those sources with the sanitizer and must run clean: exit 0,
-no sanitizer report.  (The HIP kernels cannot run under a sanitizer: there is no GPU here, and
+16-thread build, host/pt_instancing.cpp: one instanced tree laid out for instance updates) and the
+CPU restatement (oracle/pt_oracle.cpp, threaded renders) over every BASELINE scene; it is compiled
+from those sources with the sanitizer and must run clean: exit 0, no sanitizer report.  (The HIP kernels cannot run under a sanitizer: there is no GPU here, and
 GPU ASan is not available on the GPU pool.)
 """
 import os
@@ -11,10 +11,13 @@ import subprocess
 
 import pytest
 
+from helpers import tree_shape_instances, tree_shape_meshes, write_instanced_scene
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "path-tracer-cuda-opengl_amd", "host")
 SOURCES = [os.path.join(ROOT, "tests", "cpp", "sanitize_main.cpp"), os.path.join(HOST, "pt_host.cpp"),
-           os.path.join(HOST, "pt_wide8.cpp"), os.path.join(ROOT, "oracle", "pt_oracle.cpp")]
+           os.path.join(HOST, "pt_wide8.cpp"), os.path.join(HOST, "pt_instancing.cpp"),
+           os.path.join(ROOT, "oracle", "pt_oracle.cpp")]
 
 
 @pytest.mark.parametrize("kind,flags,light", [
@@ -28,6 +31,9 @@ def test_sanitized_host_and_oracle(tmp_path, kind, flags, light):
                     *SOURCES, "-lz", "-o", exe], check=True)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
                TSAN_OPTIONS="halt_on_error=1")
+    meshes, mats = tree_shape_meshes()   # the instanced section's input: the 9-instance scene of test_inst_build.py
+    m, mesh, _ = tree_shape_instances(9, seed=31)
+    write_instanced_scene(tmp_path, meshes, mats, m, mesh)
     args = [exe, os.path.join(ROOT, "models"), str(tmp_path)] + (["light"] if light else [])
     r = subprocess.run(args, capture_output=True, text=True, timeout=900, env=env)
     report = r.stdout + r.stderr
