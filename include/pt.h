@@ -47,6 +47,48 @@ enum { PT_LAMBERTIAN = 1, PT_METAL = 2, PT_DIELECTRIC = 4, PT_EMISSIVE = 8 };
  * is exact while N * R < 2^31, so 1024 keeps 2^21 accumulated samples per pixel safe (next to the
  * "at most 2^24 - 1 accumulated samples" of PT_RENDER_ACCUMULATE, which holds for radiance <= 128). */
 #define PT_MAX_RADIANCE 1024.0f
+/* PT_RENDER_NEE (pt_render_opts.flags): next-event estimation, direct sampling of the emissive
+ * triangles.  The reference's Lambertian scatters along n + unit vector, exactly cosine-weighted with
+ * attenuation = albedo, so a light sample weighted with the Lambert BRDF albedo / pi has the blind
+ * integrator's expectation; the rule below adds it to the loop and takes the same light out of the
+ * scattered ray.  Without the flag nothing changes.
+ * Lights: the scene's objects of type PT_TRIANGLE whose material is PT_EMISSIVE, in object-index
+ *   order, nL of them (pt_scene_light_count), listed on the device by every pt_scene_build_bvh* (so
+ *   after pt_scene_update_objects too) as {v0, e1 = v1 - v0, e2 = v2 - v0, E}.  Emissive spheres are
+ *   not sampled; they emit when hit, as ever.
+ * nL == 0: the flag changes nothing at all (image bits, RNG streams, counters; no clamp either).
+ * Where: at a hit on a PT_LAMBERTIAN material, after its scatter, when the path goes on (bounces
+ *   left; a path out of bounces ends with sky x attenuation and takes no light sample).
+ * Draws: three more curand_uniform values of the path's stream, after the material's own: uL, ua, ub
+ *   -- always, whatever the geometry tests below say.
+ * Every operation below is one rounded fp32 operation, in this order (dot(a, b) = (a.x * b.x + a.y *
+ * b.y) + a.z * b.z; cross(u, v) = (u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x)):
+ *   k = min((int)(uL * (float)nL), nL - 1);   if (ua + ub > 1) { ua = 1 - ua; ub = 1 - ub; }
+ *   ub = fminf(ub, 1 - ua);   ua = fminf(ua, 1 - ub)      (the fold's sum is a rounded one: a point it
+ *   left up to 2^-24 outside the edge ua + ub = 1 moves onto it; then ua, ub >= 0 and ua + ub <= 1 hold
+ *   exactly -- 1 - x is exact for x >= 0.5, and a pair of values below 0.5 needs no help)
+ *   q = (v0 + ua * e1) + ub * e2;   w = q - p          (p = the hit point, the scatter ray's origin)
+ *   cs = dot(n, w)   (n = the hit's normal, facing the incoming ray);   cl = |dot(cross(e1, e2), w)|;
+ *   d2 = dot(w, w).   cs <= 0, cl == 0 or d2 == 0: no shadow ray, nothing added.
+ *   Shadow ray (p, w), unnormalised: occluded exactly when pt_trace_closest_ex(tmin = 0.001, tmax =
+ *   0.999) reports a hit for it (pt_trace_occluded's definition; the light sits at t = 1, the 0.001 at
+ *   either end is the reference's self-hit margin in parametric units).  It counts in pt_stats.rays
+ *   and the node / box / primitive counters like any query, not in `paths`, and uses up no bounce.
+ *   Unoccluded: G = ((cs * cl) * (float)nL) / (6.2831855f * (d2 * d2))   (|cross(e1, e2)| carries the
+ *   light's area and 1 / pdf; an IEEE division), and per channel direct += ((att * albedo) * E) * G,
+ *   att = the attenuation before this hit; a NaN channel of that product counts as 0.  `direct` is
+ *   the path's own running sum, 0 at the camera.
+ * No double counting: a ray scattered at a Lambertian hit (nL > 0) that lands on a sampled light (an
+ *   emissive triangle) ends the path with 0 instead of att * E.  Every other emitter hit is as before:
+ *   a primary hit, a hit after a metal or dielectric scatter, any hit on an emissive sphere.
+ * Clamp: a finished sample contributes fminf(direct + ending term, PT_MAX_RADIANCE) per channel (one
+ *   add, one fminf).  G is unbounded near a light; the clamp keeps the sample-mode accumulator exact
+ *   while N * PT_MAX_RADIANCE < 2^31 and is the rule's one deliberate bias.
+ * Scope: flat scenes, PT_KERNEL_WIDE / PT_KERNEL_DEFAULT and PT_KERNEL_SIMPLE, both RNG modes, with
+ *   PT_RENDER_ACCUMULATE, partitioned films and every output format.  With the flag, PT_KERNEL_WAVEFRONT
+ *   and instanced scenes are PT_ERR_INVALID and nothing is rendered (instanced lights need world-space
+ *   light records per instance). */
+#define PT_RENDER_NEE 4
 
 /* One scene object, the reference's CudaObj (cuda_object.h:16-123) without device pointers.
  * sphere: v[0..2] = centre, v[3] = radius (negative radius = hollow sphere, as in RTIOW)
@@ -247,6 +289,9 @@ int pt_scene_update_objects(pt_scene* scene, const pt_object* objs, int64_t firs
  * report such hits when r / distance falls to about 1e-4 (cancellation in its quadratic); which of
  * those are found then depends on the boxes entered, in any two builds of a scene.  A scene that was never updated builds exactly as before. */
 int pt_scene_update_instances(pt_scene* scene, const pt_instance* instances, int64_t first, int64_t n);
+/* nL, the number of sampled lights (PT_RENDER_NEE: the emissive triangles) the last build listed;
+ * 0 for an instanced scene.  PT_ERR_STATE before a build, or after an update that made it stale. */
+int pt_scene_light_count(pt_scene* scene, int64_t* n);
 /* Device time of the last pt_scene_build_bvh (HIP events around the build's stream work). */
 int pt_scene_build_time(pt_scene* scene, double* ms);
 int pt_scene_bvh_info(pt_scene* scene, int* depth, int64_t* n_nodes, int64_t* device_bytes);
@@ -349,6 +394,8 @@ int pt_render(pt_scene* scene, pt_film* film, const pt_camera* cam, int spp, int
  *   pt_film_clear() restarts the accumulation (e.g. after pt_camera_move).  At most 2^24 - 1
  *   accumulated samples per pixel.  (Sample mode's 32.32 fixed-point sums are exact while
  *   samples x radiance < 2^31: with emitters or a sky at PT_MAX_RADIANCE = 1024, 2^21 samples.)
+ *   PT_RENDER_NEE: direct light sampling of the emissive triangles (the rule above, next to
+ *   PT_EMISSIVE).  Any other bit is ignored.
  * out_format: PT_OUT_RGB32F (3 floats per pixel), PT_OUT_RGBA8 (4 bytes per pixel, quantised on
  *   the device exactly like PngImage::saveColor, png_image.h:24-30: (uint8)(clamp(c,0,0.999)*256),
  *   alpha 255; rows in film order, row 0 = bottom, pt_write_png_rgba8 flips them) or

@@ -1005,6 +1005,49 @@ __device__ __forceinline__ float3 sky(float3 d, float3 att, float3 H, float3 Z) 
 __device__ __forceinline__ float3 emitted(const HitRec& h, float3 att) {
     return h.type == PT_EMISSIVE ? mul(att, xyz(h.m0)) : f3(0.0f, 0.0f, 0.0f);
 }
+// Next-event estimation (PT_RENDER_NEE, pt.h states the rule and this operation order): the light
+// sample of a Lambertian hit at p with normal n; att = the path's attenuation after the hit (the
+// attenuation before it times the albedo).  Draws uL, ua, ub whatever follows.  true: the shadow ray
+// (p, w) is to be traced, and `term` is what an unoccluded sample adds to the path.
+constexpr float kShadowTmax = 0.999f;   // the light sits at t = 1 of the unnormalised shadow ray
+template <class G>
+__device__ __forceinline__ bool lightSample(const float4* __restrict__ lights, int nL, float3 p, float3 n, float3 att,
+                                            G& g, float3& w, float3& term) {
+    const float uL = g.uniform();
+    float ua = g.uniform(), ub = g.uniform();
+    const float nLf = (float)nL;
+    const int k = min((int)(uL * nLf), nL - 1);
+    if (ua + ub > 1.0f) { ua = 1.0f - ua; ub = 1.0f - ub; }
+    ub = fminf(ub, 1.0f - ua);   // (a sum that rounding left an ulp beyond 1: back onto the edge)
+    ua = fminf(ua, 1.0f - ub);
+    const float4* L = lights + 4 * (size_t)k;
+    const float3 v0 = xyz(L[0]), e1 = xyz(L[1]), e2 = xyz(L[2]), E = xyz(L[3]);
+    const float3 q = add(add(v0, scale(ua, e1)), scale(ub, e2));
+    w = sub(q, p);
+    const float cs = dot3(n, w);
+    const float cl = fabsf(dot3(cross3(e1, e2), w));
+    const float d2 = dot3(w, w);
+    term = f3(0.0f, 0.0f, 0.0f);
+    if (cs <= 0.0f || cl == 0.0f || d2 == 0.0f) return false;
+    const float G_ = ((cs * cl) * nLf) / (6.2831855f * (d2 * d2));   // (IEEE division)
+    const float3 t = scale(G_, mul(att, E));
+    term = f3(t.x != t.x ? 0.0f : t.x, t.y != t.y ? 0.0f : t.y, t.z != t.z ? 0.0f : t.z);
+    return true;
+}
+// The hit on shading record k is a sampled light: an emissive triangle (not an emissive sphere).
+__device__ __forceinline__ bool sampledLight(const float4* shade, int k, const HitRec& h) {
+    return h.type == PT_EMISSIVE && (__float_as_uint(shade[3 * (size_t)k + 2].y) >> 16) == 0u;
+}
+// A finished sample under NEE: the direct terms plus the path's ending term, clamped per channel.
+__device__ __forceinline__ float3 neeTotal(float3 direct, float3 contrib) {
+    const float3 t = add(direct, contrib);
+    return f3(fminf(t.x, PT_MAX_RADIANCE), fminf(t.y, PT_MAX_RADIANCE), fminf(t.z, PT_MAX_RADIANCE));
+}
+template <bool NEE>
+__device__ __forceinline__ float3 endOf(float3 direct, float3 contrib) {
+    if constexpr (NEE) return neeTotal(direct, contrib);
+    else return contrib;
+}
 
 // ------------------------------------------------------------------------ kernels
 struct RenderParams {
@@ -1062,6 +1105,10 @@ struct RenderParams {
     // sky at enqueue time (pt_scene_set_sky), by value.
     float3 skyH, skyZ;
     int lit;
+    // PT_RENDER_NEE (pt.h) on a scene with sampled lights: the light records {v0}{e1}{e2}{E} of the
+    // last build and their count nL > 0 (the kernels' NEE instantiations); 0: the rule is off.
+    const float4* lights;
+    int nLights;
 };
 template <bool LIT>
 __device__ __forceinline__ float3 skyOf(const RenderParams& P, float3 d, float3 att) {
@@ -1166,7 +1213,9 @@ __device__ __forceinline__ void lensOffset(float3 right, float3 up, float lens, 
     d = sub(d, off);
 }
 
-template <int STACK, bool SAMPLE, bool LIT = false>
+// NEE (with LIT): next-event estimation as a nested query -- the shadow ray is traced where the
+// Lambertian hit is shaded, then the loop goes on with the scatter ray.
+template <int STACK, bool SAMPLE, bool LIT = false, bool NEE = false>
 __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
     __shared__ uint32_t stk[STACK * kWave];
     const int lane = threadIdx.x;
@@ -1188,6 +1237,8 @@ __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
         float3 sum = f3(0.0f, 0.0f, 0.0f);
         float3 o, d, att;
         int depthLeft = 0, sample = 0;
+        float3 direct = f3(0.0f, 0.0f, 0.0f);   // NEE: the path's direct terms so far
+        bool fromNee = false;                    // NEE: the current ray left a hit where the rule applied
         // newPath: main.cu:284-286 + camera::get_ray (camera.h:58-64): the lens sample from the
         // path's stream (lensOffset), the time draw skipped (no moving objects on the path).
         auto newPath = [&]() {
@@ -1200,6 +1251,7 @@ __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
             att = f3(1.0f, 1.0f, 1.0f);
             depthLeft = P.max_depth;
             paths++;
+            if constexpr (NEE) { direct = f3(0.0f, 0.0f, 0.0f); fromNee = false; }
         };
         // sample mode: close summation block `b` after its last sample (its sum and its ray count,
         // the tile-cost input of the next launch's longest-first order)
@@ -1214,7 +1266,13 @@ __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
             }
         };
         if (P.max_depth <= 0) {
-            while (sample < P.spp) { newPath(); sum = add(sum, skyOf<LIT>(P, d, att)); sample++; flush(); }
+            while (sample < P.spp) {
+                newPath();
+                const float3 c0 = skyOf<LIT>(P, d, att);
+                sum = add(sum, NEE ? neeTotal(direct, c0) : c0);
+                sample++;
+                flush();
+            }
         } else if (P.spp > 0) {
             newPath();
             uint32_t* my = stk + lane;
@@ -1234,14 +1292,29 @@ __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
                     float3 na;
                     if (!scatter(P.S, h, d, na, g)) {
                         contrib = LIT ? emitted(h, att) : f3(0.0f, 0.0f, 0.0f);
+                        if constexpr (NEE) {   // the light was sampled at the hit this ray left
+                            if (fromNee && sampledLight(P.S.shade, k, h)) contrib = f3(0.0f, 0.0f, 0.0f);
+                        }
                         done = true;
                     } else {
                         att = mul(att, na);
                         o = h.p;
                         if (depthLeft == 0) { contrib = skyOf<LIT>(P, d, att); done = true; }
+                        else if constexpr (NEE) {
+                            fromNee = h.type == PT_LAMBERTIAN;
+                            if (fromNee) {
+                                float3 w, term;
+                                if (lightSample(P.lights, P.nLights, o, h.n, att, g, w, term)) {
+                                    c.rays++;
+                                    float tS = kShadowTmax;
+                                    if (trace<STACK>(P.S, o, w, 0.001f, tS, my, c) < 0) direct = add(direct, term);
+                                }
+                            }
+                        }
                     }
                 }
                 if (done) {
+                    if constexpr (NEE) contrib = neeTotal(direct, contrib);
                     sum = add(sum, contrib);
                     ++sample;
                     flush();
@@ -1379,8 +1452,17 @@ __device__ __forceinline__ float3 skyK(float3 d, float3 att) {
 // group would belong to another space), no reference-order redo (instanced frames are held to a
 // tolerance, not bit for bit).
 // LIT: scenes with an emissive material or a sky of their own (RenderParams::lit).
-template <int STACK, bool SAMPLE, bool WIDE, bool INST = false, bool LIT = false>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPerEU<STACK, SAMPLE, WIDE>))) void renderKernelWF(RenderParams P) {
+// NEE (with WIDE, LIT, not INST): next-event estimation (PT_RENDER_NEE, pt.h).  A shadow ray is an
+// ordinary query of the step machine whose `closest` starts at kShadowTmax: the SHADE step that
+// samples a light parks the scatter direction and the pending direct term in LDS and begins the
+// shadow ray from the hit point; the SHADE step that finds that query complete adds the term when
+// nothing was hit and begins the parked scatter ray.  NODE and LEAF steps do not know the difference.
+template <int STACK, bool SAMPLE, bool WIDE, bool INST = false, bool LIT = false, bool NEE = false>
+// (NEE on the deeper wide stacks, 16 and 24 entries: 4 waves per SIMD instead of 5 -- at 96 VGPRs the
+// SHADE step's light sample spilled 1-3 registers, and the 24-entry stack's 6 KB of LDS with the
+// 2.5 KB of NEE state fit 4 waves anyway)
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPerEU<STACK, SAMPLE, WIDE> - (NEE && STACK >= 16 ? 1 : 0)))) void renderKernelWF(RenderParams P) {
+    static_assert(!NEE || (WIDE && LIT && !INST), "NEE: the flat wide kernels' LIT instantiations only");
     // Deep trees (binary kernels) keep 32 stack entries per lane in LDS (8 KB per wave: 5 waves
     // per SIMD) and the rare deeper entries in global memory (stackSpill, per wave slot and lane).
     constexpr int LS = kLdsStack<STACK, SAMPLE, WIDE>;
@@ -1397,6 +1479,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     // Only SHADE steps (per sample, not per node or primitive) touch it, so it lives in LDS, not
     // in four VGPRs carried through every step.
     __shared__ uint4 taskState[SAMPLE ? kWave : 1];
+    // NEE: per lane, the path's direct terms so far [0..2], the pending direct term [3..5] and the
+    // parked scatter direction [6..8] of a shadow query, and two flag bits -- 1: the lane's current
+    // query is a shadow ray, 2: its scatter ray leaves a hit where the rule applied (a sampled light
+    // it lands on contributes nothing).  Like taskState, touched by SHADE steps only: LDS, not VGPRs
+    // carried through every NODE and LEAF step.
+    __shared__ float neeV[NEE ? 9 * kWave : 1];
+    __shared__ uint32_t neeF[NEE ? kWave : 1];
     const int lane = threadIdx.x;
     // compat mode: all spp of a pixel in order (its per-pixel XORWOW stream); one wave = one tile
     // (the longest tiles split, below).
@@ -1502,14 +1591,18 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 
     // Start the closest-hit query of (o, d).  (Macros, not lambdas: a [&] closure makes the
     // captured variables address-taken and they end up in scratch memory.)
-#define PT_BEGIN_RAY()                                                                              \
+    // SH (NEE kernels; a constant false elsewhere): the query is a shadow ray -- it starts at
+    // kShadowTmax instead of +inf, uses up no bounce and is never the camera's ray.
+#define PT_BEGIN_RAY(SH)                                                                            \
     do {                                                                                          \
-        depthLeft--;                                                                              \
+        const bool sh_ = NEE && (SH);                                                             \
+        if constexpr (NEE) depthLeft -= sh_ ? 0 : 1;                                              \
+        else depthLeft--;                                                                         \
         if constexpr (SAMPLE) {   /* rays per task: only frames that measure tile costs use them */ \
             if (kargs()->measureCost)                                                             \
                 __hip_atomic_fetch_add(&taskState[lane].w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
         }                                                                                         \
-        closest = __builtin_inff();                                                               \
+        closest = sh_ ? kShadowTmax : __builtin_inff();                                           \
         best = -1;                                                                                \
         sp = 0;                                                                                   \
         qn = 0;                                                                                   \
@@ -1520,11 +1613,14 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             oct = oc_;                                                                            \
             tg = 0u;                                                                              \
             /* sphere scenes: the best hit's window end; triangle-only: t2 (wideTestTri) */        \
-            bestLo = INST || kargs()->S.hasSpheres ? -__builtin_inff() : __builtin_inff();         \
+            /* (t2 counts the start value of a finite interval as a candidate: deferredRedo then  \
+               sends a final hit whose box entry lies beyond it to the reference-order query,    \
+               which is what wideTest's `closest < b.lo` does for the ray-query kernels) */       \
+            bestLo = INST || kargs()->S.hasSpheres ? -__builtin_inff() : closest;                  \
             ng = S.nprims > 0 ? (1u << oc_) : 0u;                                                 \
             /* only camera rays can start far from the scene (a bounce starts on a primitive), and  \
                they all start at the camera: one uniform flag, set on the host (wideFar) */     \
-            if (!INST && ((kargs()->camFar && depthLeft + 1 == kargs()->max_depth) ||              \
+            if (!INST && ((kargs()->camFar && !sh_ && depthLeft + 1 == kargs()->max_depth) ||      \
                           (PT_WIDE_MIX && mixUnsafe(inv, kargs()->S.mixLim)))) {                   \
                 ng = 0u;       /* origin far from the scene, or a direction the MIX planes */      \
                 oct |= 8u;     /* cannot take: the query in the reference's order (SHADE's redo) */ \
@@ -1683,6 +1779,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         if (Q_.cam.lens != 0.0f) lensOffset(ld3(Q_.cam.right), ld3(Q_.cam.up), Q_.cam.lens, g, o, d); \
         att = f3(1.0f, 1.0f, 1.0f);                                                               \
         depthLeft = Q_.max_depth;                                                                  \
+        if constexpr (NEE) {   /* no direct term yet, no flag */                                  \
+            neeV[0 * kWave + lane] = 0.0f; neeV[1 * kWave + lane] = 0.0f; neeV[2 * kWave + lane] = 0.0f; \
+            neeF[lane] = 0u;                                                                      \
+        }                                                                                         \
     } while (0)
 
     // The sky colour of (d, att); LIT: the scene's horizon and zenith from the kernel arguments (six
@@ -1706,7 +1806,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                     while (ts.y < ts.z) {
                         taskState[lane].y = ts.y;
                         PT_NEW_PATH();
-                        sum = add(sum, PT_SKY());
+                        sum = add(sum, endOf<NEE>(f3(0.0f, 0.0f, 0.0f), PT_SKY()));
                         ts.y++;
                         // (a kernarg pointer re-read with no user -- kargs' empty asm is volatile --
                         // that the register assignment of the sample kernels was measured with)
@@ -1722,11 +1822,11 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         if (P.max_depth <= 0) {
             for (; sample < nSamples; sample++) {
                 PT_NEW_PATH();
-                sum = add(sum, PT_SKY());
+                sum = add(sum, endOf<NEE>(f3(0.0f, 0.0f, 0.0f), PT_SKY()));
             }
         } else if (nSamples > 0) {
             PT_NEW_PATH();
-            PT_BEGIN_RAY();
+            PT_BEGIN_RAY(false);
             started = true;
         }
     }
@@ -2051,6 +2151,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             // ------------------------------------------------------------------ SHADE
             const uint64_t shadeM = mS & ~needTaskM;   // lanes whose query is complete
             const bool shading = laneOf(shadeM);
+            // NEE: the lane's flags (a lane that is not shading reads stale ones; `shading` masks them)
+            uint32_t nf = 0u;
+            if constexpr (NEE) nf = neeF[lane];
+            const bool shadowQ = NEE && (nf & 1u) != 0u;   // the finished query was a shadow ray
             if constexpr (WIDE && !INST) {
                 bool redo = shading && (oct & 8u);
 #ifdef PT_DIAG
@@ -2078,16 +2182,31 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 PT_DIAG_ADD(sRedoMiss, (uint32_t)__popcll(__ballot(missed)));
                 if (redo) {
                     const DevScene S2 = ldScene(kargs());
-                    closest = __builtin_inff();
+                    closest = shadowQ ? kShadowTmax : __builtin_inff();   // (the query's own start value)
                     const int k = traceRefStackless(S2, o, d, 0.001f, closest);
                     best = k >= 0 ? (int)S2.rankOf[k] : -1;
                 }
             }
             PT_DIAG_ADD(itS, 1u);
             bool done = false;   // the lane's sample is complete
+            bool shadowNow = false;   // NEE: the lane's next query is a shadow ray
             if (shading) {
                 float3 contrib = f3(0.0f, 0.0f, 0.0f);
-                if (best < 0) {
+                bool wasShadow = false;
+                if constexpr (NEE) {
+                    if (shadowQ) {   // the shadow query is complete: its term if nothing was hit, then the parked scatter ray
+                        if (best < 0) {
+                            neeV[0 * kWave + lane] += neeV[3 * kWave + lane];
+                            neeV[1 * kWave + lane] += neeV[4 * kWave + lane];
+                            neeV[2 * kWave + lane] += neeV[5 * kWave + lane];
+                        }
+                        d = f3(neeV[6 * kWave + lane], neeV[7 * kWave + lane], neeV[8 * kWave + lane]);
+                        neeF[lane] = nf & ~1u;
+                        wasShadow = true;
+                    }
+                }
+                if (wasShadow) {
+                } else if (best < 0) {
                     contrib = PT_SKY();
                     done = true;
                 } else {
@@ -2097,13 +2216,36 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                                             : makeHit(S, best, closest, o, d));
                     if (!scatterInto(h, d, att, g)) {
                         if constexpr (LIT) contrib = emitted(h, att);
+                        if constexpr (NEE) {   // the light was sampled at the hit this ray left
+                            if ((nf & 2u) && sampledLight(kargs()->S.wshade, best & (int)kPrimMask, h))
+                                contrib = f3(0.0f, 0.0f, 0.0f);
+                        }
                         done = true;
                     } else {
                         o = h.p;
                         if (depthLeft == 0) { contrib = PT_SKY(); done = true; }
+                        else if constexpr (NEE) {
+                            nf &= ~2u;
+                            if (h.type == PT_LAMBERTIAN) {
+                                nf |= 2u;
+                                float3 w, term;
+                                if (lightSample(kargs()->lights, kargs()->nLights, o, h.n, att, g, w, term)) {
+                                    neeV[3 * kWave + lane] = term.x; neeV[4 * kWave + lane] = term.y; neeV[5 * kWave + lane] = term.z;
+                                    neeV[6 * kWave + lane] = d.x; neeV[7 * kWave + lane] = d.y; neeV[8 * kWave + lane] = d.z;
+                                    d = w;
+                                    nf |= 1u;
+                                    shadowNow = true;
+                                }
+                            }
+                            neeF[lane] = nf;
+                        }
                     }
                 }
-                if (done) sum = add(sum, contrib);
+                if (done) {
+                    if constexpr (NEE)
+                        contrib = neeTotal(f3(neeV[0 * kWave + lane], neeV[1 * kWave + lane], neeV[2 * kWave + lane]), contrib);
+                    sum = add(sum, contrib);
+                }
             }
             // Every lane steps its sample count by `done` (a lane that is not shading by 0; shadeM
             // masks its stale state): who completed a sample and who its last one comes from two
@@ -2144,7 +2286,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #ifdef PT_DIAG
             const unsigned long long tS3 = __builtin_amdgcn_s_memtime();
 #endif
-            if (laneOf(newRayM)) PT_BEGIN_RAY();
+            if (laneOf(newRayM)) PT_BEGIN_RAY(shadowNow);
 #ifdef PT_DIAG
             const unsigned long long tS4 = __builtin_amdgcn_s_memtime();
             cycSh += tS1 - tK0; cycTk += tS2 - tS1; cycNp += tS3 - tS2; cycBr += tS4 - tS3;
@@ -2228,7 +2370,8 @@ int launchCompatWide(int stack, const void* params, hipStream_t st) {
     switch (stack) {
 #define PT_COMPAT_WIDE(S)                                                                    \
         case S:                                                                                  \
-            if (P.lit) renderKernelWF<S, false, true, false, true><<<grid, kWave, 0, st>>>(P);   \
+            if (P.nLights > 0) renderKernelWF<S, false, true, false, true, true><<<grid, kWave, 0, st>>>(P); \
+            else if (P.lit) renderKernelWF<S, false, true, false, true><<<grid, kWave, 0, st>>>(P); \
             else renderKernelWF<S, false, true><<<grid, kWave, 0, st>>>(P);                      \
             break;
         PT_COMPAT_WIDE(8)
@@ -3144,6 +3287,36 @@ __global__ __launch_bounds__(256) void leafGatherKernel(const pt_object* __restr
                                    __uint_as_float((uint32_t)o.mat), __uint_as_float(id));
 }
 
+// The sampled lights of PT_RENDER_NEE (pt.h): the emissive triangles, compacted in object order.
+// lightFlagKernel marks them, an exclusive scan (pt_prims.hpp) gives each its slot, lightListKernel
+// writes the records {v0}{e1 = v1 - v0}{e2 = v2 - v0}{E} and the count.
+__global__ __launch_bounds__(256) void lightFlagKernel(const pt_object* __restrict__ objs, int64_t n,
+                                                       const float4* __restrict__ mats, uint32_t* flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool light = objs[i].type == PT_TRIANGLE && __float_as_uint(mats[2 * objs[i].mat + 1].y) == (uint32_t)PT_EMISSIVE;
+    flag[i] = light ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void lightListKernel(const pt_object* __restrict__ objs, int64_t n,
+                                                       const float4* __restrict__ mats,
+                                                       const uint32_t* __restrict__ flag,
+                                                       const uint32_t* __restrict__ slot, uint32_t cap, float4* lights,
+                                                       uint32_t* count) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (i == n - 1) *count = slot[i] + flag[i];
+    if (!flag[i] || slot[i] >= cap) return;   // (cap: the records the host reserved; it counted the same objects)
+    const pt_object o = objs[i];
+    const float3 v0 = f3(o.v[0], o.v[1], o.v[2]), v1 = f3(o.v[3], o.v[4], o.v[5]), v2 = f3(o.v[6], o.v[7], o.v[8]);
+    const float3 e1 = sub(v1, v0), e2 = sub(v2, v0);
+    const float4 m0 = mats[2 * o.mat];
+    float4* L = lights + 4 * (size_t)slot[i];
+    L[0] = make_float4(v0.x, v0.y, v0.z, 0.0f);
+    L[1] = make_float4(e1.x, e1.y, e1.z, 0.0f);
+    L[2] = make_float4(e2.x, e2.y, e2.z, 0.0f);
+    L[3] = make_float4(m0.x, m0.y, m0.z, 0.0f);
+}
+
 // Depth of the internal hierarchy (root = 1) = the most internal ancestors of any leaf.
 __global__ __launch_bounds__(256) void depthKernel(const int* __restrict__ iparent, const int* __restrict__ lparent,
                                                    int n, int* depth) {
@@ -3317,6 +3490,11 @@ struct pt_scene {
     float sceneCE[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // tight scene box: centre, largest extent (DevScene)
     float skyH[3] = {1.0f, 1.0f, 1.0f}, skyZ[3] = {0.5f, 0.7f, 1.0f};   // pt_scene_set_sky (default: main.cu:34-36)
     bool hasEmissive = false;               // any PT_EMISSIVE material
+    // PT_RENDER_NEE: the sampled lights (emissive triangles) of the last build, listed on the device
+    // (lightFlagKernel, a scan, lightListKernel); the buffers are kept between builds
+    std::vector<uint8_t> matEmissive;       // per material: its type is PT_EMISSIVE
+    DevBuf lights, lightFlag, lightSlot, lightScan, lightCount;
+    int64_t nLights = 0;
     float mixLim = -1.0f;                          // DevScene::mixLim (-1: every ray takes the reference order)
     // instanced scenes (pt_scene_create_instanced): meshes = object ranges of `objs`, instances
     bool instanced = false;
@@ -3641,8 +3819,17 @@ void launchRenderWide(const RenderParams& P, hipStream_t st) {
         else renderKernelWF<S, false, true, true, LIT><<<P.compatGrid, kWave, 0, st>>>(P);
         return;
     }
-    if (P.pixAcc) renderKernelWF<S, true, true, false, LIT><<<P.nwaves, kWave, 0, st>>>(P);
-    else pt::launchCompatWide(S, &P, st);   // (its own translation unit, pt_compat.hip; reads P.lit)
+    if (P.pixAcc) {
+        if constexpr (LIT) {   // (NEE launches are LIT: a sampled light is an emissive material)
+            if (P.nLights > 0) {
+                renderKernelWF<S, true, true, false, true, true><<<P.nwaves, kWave, 0, st>>>(P);
+                return;
+            }
+        }
+        renderKernelWF<S, true, true, false, LIT><<<P.nwaves, kWave, 0, st>>>(P);
+    } else {
+        pt::launchCompatWide(S, &P, st);   // (its own translation unit, pt_compat.hip; reads P.lit, P.nLights)
+    }
 }
 template <int S, bool LIT>
 void launchRender(const RenderParams& P, hipStream_t st) {
@@ -3650,6 +3837,8 @@ void launchRender(const RenderParams& P, hipStream_t st) {
         renderKernelWF<S, true, false, false, LIT><<<P.nwaves, kWave, 0, st>>>(P);
     else if (P.kernel == PT_KERNEL_WAVEFRONT)
         renderKernelWF<S, false, false, false, LIT><<<P.compatGrid, kWave, 0, st>>>(P);
+    else if (LIT && P.nLights > 0 && P.pixAcc) renderKernel<S, true, LIT, LIT><<<P.ntiles, kWave, 0, st>>>(P);
+    else if (LIT && P.nLights > 0) renderKernel<S, false, LIT, LIT><<<P.ntiles, kWave, 0, st>>>(P);
     else if (P.pixAcc) renderKernel<S, true, LIT><<<P.ntiles, kWave, 0, st>>>(P);
     else renderKernel<S, false, LIT><<<P.ntiles, kWave, 0, st>>>(P);
 }
@@ -3676,8 +3865,19 @@ bool withBinStack(int stack, F f) { return withStack<16, 24, 32, 48, 64, 80>(sta
 // the same LDS and waves-per-SIMD attribute, so the same occupancy (DESIGN.md's resource table).
 // The compat wide kernels live in pt_compat.hip's
 // translation unit.
-int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample) {
+int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, bool nee) {
     const bool wide = kernel == PT_KERNEL_WIDE;
+    if (wide && !inst && sample && nee) {   // the NEE kernels hold more LDS per wave: asked of themselves
+        int rc = PT_OK;
+        const bool ok = withWideStack(stack, [&](auto N) {
+            constexpr int K = decltype(N)::value;
+            const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                &n, reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true>), kWave, 0);
+            if (e != hipSuccess) rc = fail(PT_ERR_HIP, std::string("hipOccupancyMaxActiveBlocksPerMultiprocessor: ") + hipGetErrorString(e));
+        });
+        if (!ok) return fail(PT_ERR_STATE, "unsupported wide BVH depth");
+        return rc;
+    }
     if (wide && !inst && !sample)
         return pt::compatWideWavesPerCU(stack, n) ? fail(PT_ERR_STATE, "unsupported wide BVH depth") : PT_OK;
     int rc = PT_OK;
@@ -3880,6 +4080,8 @@ int pt_scene_create(int device, const pt_object* objs, int64_t n, const pt_mater
     s->nobj = n;
     s->nmat = nmat;
     s->hasEmissive = emissive;
+    s->matEmissive.resize((size_t)nmat);
+    for (int64_t i = 0; i < nmat; i++) s->matEmissive[(size_t)i] = mats[i].type == PT_EMISSIVE ? 1 : 0;
     s->objs.assign(objs, objs + n);
     for (int64_t i = 0; i < n && !s->hasSpheres; i++) s->hasSpheres = objs[i].type == PT_SPHERE;
     // materials: (albedo.xyz, fuzz), (ir, type, 0, 0)
@@ -4023,6 +4225,18 @@ int pt_scene_build_bvh_ex(pt_scene* s, int flags, void* stream) {
         (rc = devReserve(ids2, n1 * 4)) || (rc = devReserve(box6, (1 + kBoxBlocks) * 6 * sizeof(float))) || (rc = devReserve(sph, n1 * 4)) ||
         (rc = devReserve(arr, ni * 4)) || (rc = devReserve(dep, 16)))
         return rc;
+    // The sampled lights (PT_RENDER_NEE): the host counts them to size the list (it allocates only when
+    // the count or the object count grows); the list itself is the device's, on the build's stream.
+    s->nLights = 0;
+    uint32_t lightCap = 0;
+    if (s->hasEmissive)
+        for (int64_t i = 0; i < n; i++)
+            lightCap += (s->objs[(size_t)i].type == PT_TRIANGLE && s->matEmissive[(size_t)s->objs[(size_t)i].mat]) ? 1u : 0u;
+    if (lightCap > 0 &&
+        ((rc = devReserve(s->lightFlag, n1 * 4)) || (rc = devReserve(s->lightSlot, n1 * 4)) ||
+         (rc = devReserve(s->lightScan, pt::scanScratchBytesU32(n1))) ||
+         (rc = devReserve(s->lights, (size_t)lightCap * 4 * sizeof(float4))) || (rc = devReserve(s->lightCount, 16))))
+        return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // Every return path destroys the events and, on failure, waits for the work already queued on
     // the stream (it uses the scene's buffers).
@@ -4061,6 +4275,15 @@ int pt_scene_build_bvh_ex(pt_scene* s, int flags, void* stream) {
                                             s->shade.as<float4>(), s->leafBoxes.as<float>(), sph.as<uint32_t>(),
                                             s->mats.as<float4>());
         HIP_TRY(hipGetLastError());
+        if (lightCap > 0) {
+            lightFlagKernel<<<nb, tb, 0, st>>>(s->dobjs.as<pt_object>(), n, s->mats.as<float4>(), s->lightFlag.as<uint32_t>());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(pt::exclusiveScanU32(s->lightScan.p, s->lightFlag.as<uint32_t>(), s->lightSlot.as<uint32_t>(), (size_t)n, st));
+            lightListKernel<<<nb, tb, 0, st>>>(s->dobjs.as<pt_object>(), n, s->mats.as<float4>(), s->lightFlag.as<uint32_t>(),
+                                               s->lightSlot.as<uint32_t>(), lightCap, s->lights.as<float4>(),
+                                               s->lightCount.as<uint32_t>());
+            HIP_TRY(hipGetLastError());
+        }
     }
     HIP_TRY(hipMemsetAsync(s->nodes.p, 0, ni * 4 * sizeof(float4), st));
     HIP_TRY(hipMemsetAsync(s->iparent.p, 0xff, ni * 4, st));
@@ -4096,6 +4319,12 @@ int pt_scene_build_bvh_ex(pt_scene* s, int flags, void* stream) {
     int depth = 0;
     HIP_TRY(hipMemcpy(&depth, dep.p, 4, hipMemcpyDeviceToHost));
     s->depth = n > 1 ? depth : 0;
+    if (lightCap > 0) {
+        uint32_t nl = 0;
+        HIP_TRY(hipMemcpy(&nl, s->lightCount.p, 4, hipMemcpyDeviceToHost));
+        if (nl != lightCap) return fail(PT_ERR_STATE, "pt_scene_build_bvh: the device's light list disagrees with the host's count");
+        s->nLights = (int64_t)nl;
+    }
     if (n > 0) {   // the tight scene box: union of the root's child boxes (a single object: its box)
         float mn[3], mx[3];
         if (n > 1) {
@@ -4153,6 +4382,13 @@ int pt_scene_wide_info(pt_scene* s, int* depth, int64_t* slots, double* ms, int*
     if (slots) *slots = ok ? s->wideNodes : 0;
     if (ms) *ms = ok ? s->wideBuildMs : 0.0;
     if (source) *source = ok ? s->wideSource : 0;
+    return PT_OK;
+}
+
+int pt_scene_light_count(pt_scene* s, int64_t* n) {
+    if (!s || !n) return fail(PT_ERR_INVALID, "pt_scene_light_count: null argument");
+    if (!s->built) return fail(PT_ERR_STATE, "pt_scene_light_count: BVH not built");
+    *n = s->nLights;
     return PT_OK;
 }
 
@@ -4442,6 +4678,7 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     if (fmt != PT_OUT_RGB32F && fmt != PT_OUT_RGBA8 && fmt != PT_OUT_RGBA8_SURFACE)
         return fail(PT_ERR_INVALID, "pt_render_ex: unknown output format");
     const bool accumulate = opts && (opts->flags & PT_RENDER_ACCUMULATE);
+    const bool neeFlag = opts && (opts->flags & PT_RENDER_NEE);
     const size_t outBpp = fmt == PT_OUT_RGB32F ? 12 : 4;
     if (accumulate && f->accumSamples + spp >= (1ll << 24))
         return fail(PT_ERR_INVALID, "pt_render_ex: accumulated samples must stay below 2^24");
@@ -4457,6 +4694,12 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
         return fail(PT_ERR_INVALID, "pt_render_ex: unknown kernel");
     if (s->instanced && kernel != PT_KERNEL_WIDE)
         return fail(PT_ERR_INVALID, "pt_render_ex: instanced scenes render with the wide kernel (PT_KERNEL_WIDE)");
+    if (neeFlag && s->instanced)
+        return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_NEE is not available on instanced scenes (flat scenes only)");
+    if (neeFlag && kernel == PT_KERNEL_WAVEFRONT)
+        return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_NEE is not available with PT_KERNEL_WAVEFRONT "
+                                    "(PT_KERNEL_WIDE, PT_KERNEL_DEFAULT or PT_KERNEL_SIMPLE)");
+    const bool nee = neeFlag && s->nLights > 0;   // (no sampled light: the flag changes nothing)
     const int rng = opts ? opts->rng : PT_RNG_COMPAT;
     if (rng != PT_RNG_COMPAT && rng != PT_RNG_SAMPLE) return fail(PT_ERR_INVALID, "pt_render_ex: unknown rng mode");
     if (kernel == PT_KERNEL_WIDE && (rc = ensureWide(s))) return rc;   // (first use: builds the tree)
@@ -4495,6 +4738,8 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
         static const float H0[3] = {1.0f, 1.0f, 1.0f}, Z0[3] = {0.5f, 0.7f, 1.0f};
         P.lit = (s->hasEmissive || std::memcmp(s->skyH, H0, sizeof(H0)) != 0 || std::memcmp(s->skyZ, Z0, sizeof(Z0)) != 0) ? 1 : 0;
     }
+    P.lights = nee ? s->lights.as<float4>() : nullptr;
+    P.nLights = nee ? (int)s->nLights : 0;
     uint32_t* b = f->state.as<uint32_t>();
     P.sd = b; P.s0 = b + np; P.s1 = b + 2 * np; P.s2 = b + 3 * np; P.s3 = b + 4 * np; P.s4 = b + 5 * np;
     P.out = static_cast<float*>(dst);
@@ -4590,16 +4835,16 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     // occupancy per CU, which the LDS stack caps on deep trees.  Queried once per (device, kernel
     // instantiation) and process.
     auto perCUFor = [&](int& perCU) -> int {
-        static std::atomic<int> cached[16][2][2][2][3];   // [device][sample][instanced][wide][stack 8, 16, 24]
+        static std::atomic<int> cached[16][2][2][2][3][2];   // [device][sample][instanced][wide][stack 8, 16, 24][nee]
         const bool small = stack <= 24 && stack % 8 == 0 && f->device >= 0 && f->device < 16;
         std::atomic<int>* c = small ? &cached[f->device][sample ? 1 : 0][s->instanced ? 1 : 0]
-                                             [kernel == PT_KERNEL_WIDE ? 1 : 0][stack / 8 - 1] : nullptr;
+                                             [kernel == PT_KERNEL_WIDE ? 1 : 0][stack / 8 - 1][nee ? 1 : 0] : nullptr;
         const int known = c ? c->load(std::memory_order_relaxed) : 0;
         if (known > 0) {
             perCU = known;
             return PT_OK;
         }
-        if (int r = persistentWavesPerCU(stack, kernel, perCU, s->instanced, sample)) return r;
+        if (int r = persistentWavesPerCU(stack, kernel, perCU, s->instanced, sample, nee)) return r;
         if (c) c->store(perCU, std::memory_order_relaxed);
         return PT_OK;
     };
@@ -4615,7 +4860,8 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     P.critList = nullptr;
     P.critFlag = nullptr;
     P.pixRays = nullptr;
-    const bool critOn = lpt && critFor(sample, kernel == PT_KERNEL_WIDE, s->instanced, stack) && np > 0 &&
+    // (not in NEE launches: the per-lane loop knows no shadow query; the waves only schedule)
+    const bool critOn = lpt && !nee && critFor(sample, kernel == PT_KERNEL_WIDE, s->instanced, stack) && np > 0 &&
                         max_depth > 16 && envCount("PT_CRIT_PIXELS", kCritPixels) > 0;
     if (critOn) {
         if ((rc = devReserve(f->pixRays, (size_t)np * 4))) return rc;

@@ -58,6 +58,7 @@ class RenderOpts(C.Structure):
 
 RNG_COMPAT, RNG_SAMPLE = 0, 1
 IDENTITY_ORDER, ACCUMULATE = 1, 2
+NEE = 4   # PT_RENDER_NEE: next-event estimation (direct sampling of the emissive triangles)
 OUT_RGB32F, OUT_RGBA8, OUT_RGBA8_SURFACE = 0, 1, 2
 
 
@@ -92,7 +93,7 @@ EXPORTS = [
     "pt_scene_update_objects", "pt_trace_closest_ex", "pt_scene_wide_info", "pt_trace_closest_device",
     "pt_scene_build_bvh_ex", "pt_film_stats", "pt_preset_instanced", "pt_instanced_desc_free",
     "pt_scene_create_instanced", "pt_trace_occluded", "pt_trace_occluded_device",
-    "pt_scene_update_instances", "pt_scene_set_sky", "pt_preset_sky",
+    "pt_scene_update_instances", "pt_scene_set_sky", "pt_preset_sky", "pt_scene_light_count",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -132,6 +133,7 @@ _sig = {
     "pt_scene_build_bvh_ex": (C.c_int, [_P, C.c_int, _P]),
     "pt_film_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "pt_scene_build_time": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "pt_scene_light_count": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "pt_scene_update_objects": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
     "pt_scene_update_instances": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
     "pt_scene_bvh_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -380,6 +382,14 @@ class Scene:
                "pt_scene_set_sky")
 
     @property
+    def n_lights(self) -> int:
+        """pt_scene_light_count: the sampled lights (emissive triangles) the last build listed, what
+        render(nee=True) samples; PtError (PT_ERR_STATE) before a build or after update_objects."""
+        n = C.c_int64()
+        _check(lib.pt_scene_light_count(self.h, C.byref(n)), "pt_scene_light_count")
+        return n.value
+
+    @property
     def build_ms(self) -> float:
         """Device time of the last LBVH build (HIP events)."""
         ms = C.c_double()
@@ -523,16 +533,20 @@ class Film:
 def render(scene: Scene, film: Film, camera: Camera, spp: int, max_depth: int, out=None, stream=None,
            kernel: int = KERNEL_DEFAULT, leaf_batch: int = 0, shade_batch: int = 0, rng: int = RNG_COMPAT,
            chunk: int = 0, flags: int = 0, accumulate: bool = False, out_format: int = OUT_RGB32F,
-           wait: bool = True):
+           wait: bool = True, nee: bool = False):
     """Render spp samples per pixel of the film's rows.  `out` may be a numpy array (host) or
     an integer device pointer (then `stream` is a hipStream_t handle or None).  Returns
     (rgb or None, Stats); rgb is float32 (n_pixels, 3), or uint8 (n_pixels, 4) for the 8-bit
     output formats.  accumulate=True adds the frame to the film's running sums (progressive).
+    nee=True sets PT_RENDER_NEE: direct light sampling of the scene's emissive triangles (pt.h states
+    the rule; flat scenes, the wide and simple kernels; nothing changes when scene.n_lights == 0).
     wait=False (device output only): the frame is enqueued and the call returns at once with
     Stats None -- film.stats() waits for it and returns its counters."""
     st = Stats()
     if accumulate:
         flags |= ACCUMULATE
+    if nee:
+        flags |= NEE
     opts = RenderOpts(kernel, leaf_batch, shade_batch, flags, rng, chunk, out_format, 0)
     if out is None or isinstance(out, np.ndarray):
         if out is None:
