@@ -304,7 +304,34 @@ int pt_scene_wide_info(pt_scene* scene, int* depth, int64_t* node_slots, double*
 /* Download the LBVH in the reference's node layout (2n-1 nodes). */
 int pt_scene_download_bvh(pt_scene* scene, pt_bvh_node* nodes);
 /* RenderManager::hitBvh (render_manager.h:86-135) over a batch of rays, t in [tmin, tmax).
- * rays/hits are host pointers. */
+ * rays/hits are host pointers.
+ *
+ * The contract of the five ray-query entry points (pt_trace_closest, _ex, _device, pt_trace_occluded,
+ * _device) on degenerate input (tests/test_gpu_degenerate_rays.py):
+ * 1. Rays.  Any bit pattern in o and d is legal: NaN (quiet or signalling), infinities, zero and
+ *    denormal directions, magnitudes that overflow the primitive tests.  A query never fails, never
+ *    trips the traversal guard (PT_ERR_STATE) and always ends; a ray's result does not depend on the
+ *    other rays of its batch.
+ * 2. The rule.  The result is the reference's (RenderManager::hitBvh with CudaObj::hit, in its own
+ *    fp32 operation order) with one change: a candidate whose t is NaN is not a hit.  The reference
+ *    accepts such a candidate by accident of its comparison forms (every rejection is a comparison,
+ *    and a NaN fails them all), keeps the NaN as its closest distance -- after which every box passes
+ *    and every later candidate replaces the record -- and returns a record of NaNs; the kernels here
+ *    have always rejected it (their accept test is t >= 0), at no cost.  Consequences: a ray with a
+ *    NaN in any component of o or d misses everything (NaN * 0 is NaN, so the NaN reaches the t of
+ *    every triangle and sphere test; the same after an instance's transform) and gets the miss
+ *    record {0, -1, -1, 0, 0...}; so does the all-zero direction.  Infinite values are not special:
+ *    t = +inf is a hit when the reference's arithmetic says so (a sphere root of a denormal or
+ *    overflowing direction with tmax = +inf), with the p and n its arithmetic gives.  A scene of one
+ *    primitive has no box test in the reference, so such a hit counts there whatever the box.
+ * 3. Interval.  tmin must be >= 0 and not NaN (-0.0 counts as 0), and the scalar tmax must not be
+ *    NaN: otherwise PT_ERR_INVALID before anything is launched, with hits / occluded and stats left
+ *    untouched and a message "<function>: tmin must be >= 0 and not NaN" or "<function>: tmax must
+ *    not be NaN".  (A negative tmin would ask for hits behind the origin, which the kernels' accept
+ *    test excludes.)  tmax < tmin is legal: an empty interval, every ray misses -- a negative tmax
+ *    and a scene of one primitive included.  Where ray_tmax is given the scalar tmax is ignored,
+ *    whatever it holds, and a ray_tmax[i] that is NaN counts as +inf, no upper bound for that ray
+ *    (it cannot be checked without a pass over device memory). */
 int pt_trace_closest(pt_scene* scene, const pt_ray* rays, int64_t n, float tmin, float tmax,
                      pt_hit* hits, pt_stats* stats);
 /* pt_trace_closest with a choice of tree: PT_KERNEL_WIDE traverses the compressed 8-wide tree
@@ -320,7 +347,9 @@ int pt_trace_closest_device(pt_scene* scene, const pt_ray* rays, int64_t n, floa
  * (same scene, tmin and tmax; so a triangle at exactly t == tmax does not occlude and a sphere
  * root at exactly tmax does), found without the hit record and without walking on after the
  * first blocker.  ray_tmax, when not NULL, gives each ray its own tmax (shadow rays: the distance
- * to the light) and the scalar tmax is ignored.  kernel: PT_KERNEL_DEFAULT and PT_KERNEL_WIDE
+ * to the light) and the scalar tmax is ignored.  Degenerate rays and intervals: pt_trace_closest's
+ * contract (any ray is legal and a NaN candidate is no hit; tmin < 0, a NaN tmin or a NaN scalar tmax
+ * is PT_ERR_INVALID with `occluded` untouched; a NaN ray_tmax[i] counts as +inf).  kernel: PT_KERNEL_DEFAULT and PT_KERNEL_WIDE
  * traverse the compressed 8-wide tree (built at first use; the answer has no order to honour, so
  * the fast tree is the default), PT_KERNEL_SIMPLE / PT_KERNEL_WAVEFRONT the binary LBVH in the
  * reference's order (PT_ERR_INVALID on an instanced scene).  rays / ray_tmax / occluded are host

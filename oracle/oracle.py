@@ -53,6 +53,8 @@ for name, res, args in [
     ("orc_build_lbvh", C.c_int, [_P, C.c_int64, _P, C.c_int, _P]),
     ("orc_bvh_depth", C.c_int, [_P, C.c_int64]),
     ("orc_trace", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int, _P, C.POINTER(Stats)]),
+    ("orc_trace2", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_int, _P,
+                             C.POINTER(Stats)]),
     ("orc_scatter_tape", C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_int), _P, _P]),
     ("orc_render2", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int,
                               C.c_int, _P, _P, C.POINTER(Stats), C.c_int, _P]),
@@ -139,14 +141,15 @@ def bvh_depth(nodes: np.ndarray, n: int) -> int:
     return lib.orc_bvh_depth(_ptr(nodes), n)
 
 
-def trace(objects, nodes, rays: np.ndarray, tmin=0.001, tmax=float("inf"), brute=False):
-    """rays: float32 (n, 6) = origin, direction."""
+def trace(objects, nodes, rays: np.ndarray, tmin=0.001, tmax=float("inf"), brute=False, nan_miss=False):
+    """rays: float32 (n, 6) = origin, direction.  nan_miss=True: the library's rule (include/pt.h,
+    pt_trace_closest) -- the reference's, except that a candidate whose t is NaN is not a hit."""
     objects = np.ascontiguousarray(objects, OBJECT_DTYPE)
     rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
     hits = np.zeros(len(rays), HIT_DTYPE)
     st = Stats()
-    lib.orc_trace(_ptr(objects), len(objects), _ptr(nodes), _ptr(rays), len(rays), tmin, tmax, int(brute),
-                  _ptr(hits), C.byref(st))
+    lib.orc_trace2(_ptr(objects), len(objects), _ptr(nodes), _ptr(rays), len(rays), tmin, tmax, int(brute),
+                   int(nan_miss), _ptr(hits), C.byref(st))
     return hits, st
 
 

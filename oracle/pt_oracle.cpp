@@ -160,15 +160,21 @@ bool objectHit(const orc_object& o, int id, const Ray& r, float tmin, float tmax
 
 // RenderManager::hitBvh, render_manager.h:86-135 (same visiting order: left child box, right
 // child box, leaves tested immediately, internal children pushed left-then-right).
+// nanMiss (orc_trace2, off everywhere else): a candidate whose t is NaN is not a hit.  The reference
+// accepts it -- all its rejections are comparisons, which a NaN fails -- and `closest` then stays NaN,
+// so every later box passes and every later candidate replaces the record.
 bool hitBvh(const orc_object* objs, int64_t n, const orc_node* bvh, const Ray& r, float tmin, float tmax,
-            Hit& rec, orc_stats* st) {
+            Hit& rec, orc_stats* st, bool nanMiss = false) {
     if (n <= 0) return false;
     float closest = tmax;
     bool any = false;
     Hit tmp;
     const orc_node* cur = &bvh[0];
     if (cur->objid != -1) {                                                           // :92-98
-        if (objectHit(objs[cur->objid], cur->objid, r, tmin, closest, tmp, st)) { any = true; rec = tmp; }
+        if (objectHit(objs[cur->objid], cur->objid, r, tmin, closest, tmp, st) && !(nanMiss && std::isnan(tmp.t))) {
+            any = true;
+            rec = tmp;
+        }
         return any;
     }
     V3 inv = v3(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
@@ -184,7 +190,8 @@ bool hitBvh(const orc_object* objs, int64_t n, const orc_node* bvh, const Ray& r
             if (st) st->box_tests++;
             if (boxHit(nx.bmin, nx.bmax, r, inv, tmin, closest)) {
                 if (nx.objid != -1) {
-                    if (objectHit(objs[nx.objid], nx.objid, r, tmin, closest, tmp, st)) {
+                    if (objectHit(objs[nx.objid], nx.objid, r, tmin, closest, tmp, st) &&
+                        !(nanMiss && std::isnan(tmp.t))) {
                         any = true;
                         closest = tmp.t;
                         rec = tmp;
@@ -199,12 +206,12 @@ bool hitBvh(const orc_object* objs, int64_t n, const orc_node* bvh, const Ray& r
 }
 
 // RenderManager::hit (brute force), render_manager.h:71-84
-bool hitBrute(const orc_object* objs, int64_t n, const Ray& r, float tmin, float tmax, Hit& rec) {
+bool hitBrute(const orc_object* objs, int64_t n, const Ray& r, float tmin, float tmax, Hit& rec, bool nanMiss = false) {
     Hit tmp;
     bool any = false;
     float closest = tmax;
     for (int64_t i = 0; i < n; i++) {
-        if (objectHit(objs[i], (int)i, r, tmin, closest, tmp, nullptr)) {
+        if (objectHit(objs[i], (int)i, r, tmin, closest, tmp, nullptr) && !(nanMiss && std::isnan(tmp.t))) {
             any = true;
             closest = tmp.t;
             rec = tmp;
@@ -601,10 +608,17 @@ int orc_bvh_depth(const orc_node* nodes, int64_t n) {
 
 int orc_trace(const orc_object* objs, int64_t nobj, const orc_node* nodes, const float* rays, int64_t nrays,
               float tmin, float tmax, int brute, orc_hit* hits, orc_stats* stats) {
+    return orc_trace2(objs, nobj, nodes, rays, nrays, tmin, tmax, brute, 0, hits, stats);
+}
+
+int orc_trace2(const orc_object* objs, int64_t nobj, const orc_node* nodes, const float* rays, int64_t nrays,
+               float tmin, float tmax, int brute, int nan_miss, orc_hit* hits, orc_stats* stats) {
+    const bool nm = nan_miss != 0;
     for (int64_t i = 0; i < nrays; i++) {
         Ray r{load3(rays + 6 * i), load3(rays + 6 * i + 3)};
         Hit h;
-        bool ok = brute ? hitBrute(objs, nobj, r, tmin, tmax, h) : hitBvh(objs, nobj, nodes, r, tmin, tmax, h, stats);
+        bool ok = brute ? hitBrute(objs, nobj, r, tmin, tmax, h, nm)
+                        : hitBvh(objs, nobj, nodes, r, tmin, tmax, h, stats, nm);
         if (stats) stats->rays++;
         orc_hit& o = hits[i];
         std::memset(&o, 0, sizeof(o));

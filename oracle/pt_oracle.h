@@ -60,6 +60,11 @@ int orc_bvh_depth(const orc_node* nodes, int64_t n);
 /* utils/render_manager.h:71-135: closest hit, t in [tmin, tmax).  rays: n x {o[3], d[3]} */
 int orc_trace(const orc_object* objs, int64_t nobj, const orc_node* nodes, const float* rays,
               int64_t nrays, float tmin, float tmax, int brute, orc_hit* hits, orc_stats* stats);
+/* orc_trace with the library's one change to the reference's rule (include/pt.h, pt_trace_closest):
+ * nan_miss != 0: a candidate whose t is NaN is not a hit, in the traversal and in the brute-force
+ * loop alike.  nan_miss == 0 is orc_trace. */
+int orc_trace2(const orc_object* objs, int64_t nobj, const orc_node* nodes, const float* rays,
+               int64_t nrays, float tmin, float tmax, int brute, int nan_miss, orc_hit* hits, orc_stats* stats);
 
 /* simulation/material.h:28-61 driven by a tape of uniforms; returns scatter() */
 int orc_scatter_tape(const orc_material* m, const float ray[6], const orc_hit* rec,

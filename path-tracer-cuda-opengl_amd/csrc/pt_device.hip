@@ -2599,8 +2599,8 @@ struct WideWalk {
     uint32_t visits;   // the query's node visits: read by traceKernelWideQ under PT_TRACE_DIAG_VISITS only, else dead
 };
 // The query's start: the walk's state and `hi`, the interval's (shifted) upper bound.  true: a far
-// origin, or a direction the MIX planes cannot take; the walk is empty and the caller answers the
-// query in the reference's order.
+// origin, a direction the MIX planes cannot take, or a scene of one primitive; the walk is empty and
+// the caller answers the query in the reference's order.
 template <bool INST>
 __device__ __forceinline__ bool wideStart(const DevScene& S, pt_ray r, float tmin, float tmax, WideWalk& w, float& hi,
                                           Counters& c) {
@@ -2611,7 +2611,10 @@ __device__ __forceinline__ bool wideStart(const DevScene& S, pt_ray r, float tmi
     w.o = wo; w.d = w.wd; w.inv = w.winv;
     w.oct = w.woct;
     w.inst = 0u;
-    const bool far = !INST && (wideFar(S, w.o) || (PT_WIDE_MIX && mixUnsafe(w.winv, S.mixLim)));
+    // (a single primitive is the reference's root: tested with no box test at all (:92-98), so a hit its
+    // arithmetic reports outside the primitive's box -- t = +inf from an overflowing direction, say --
+    // counts; the wide root's box test would drop it, the reference-order query has none)
+    const bool far = !INST && (S.nprims == 1 || wideFar(S, w.o) || (PT_WIDE_MIX && mixUnsafe(w.winv, S.mixLim)));
     // instanced: a far origin moves to the ray's entry into the world (instEntry); distances
     // are then measured from there and shifted back at the end
     w.wo2 = wo;
@@ -2905,7 +2908,18 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_
 // traceRefStackless) and the wide planes never reject a box the exact test accepts (wideHits).
 // So the walk keeps the interval fixed and stops at the first primitive that passes (a) and (b):
 // the closest-hit kernels' walk up to their first accepted hit, hence never more work.
-// rayTmax (optional): per-ray tmax, replacing the scalar.
+// rayTmax (optional): per-ray tmax, replacing the scalar.  A NaN entry is no upper bound (include/pt.h)
+// and is replaced by +inf where it is read, so no later test sees it.  Left in place it is +inf to
+// every `bound < x` comparison and NaN-ignoring min, with two exceptions: a signalling NaN (in IEEE
+// mode v_min_f32 / v_min3_f32 return NaN for a signalling operand, and the wide node test's raw
+// v_min3_f32, min3Raw, then rejects every box), and a node all of whose far planes are NaN (an
+// instanced scene's ray with three zero or denormal direction components: min(NaN planes, NaN) is
+// NaN where min(NaN planes, inf) is inf).
+__device__ __forceinline__ float rayTmaxOf(const float* __restrict__ rayTmax, int64_t ray, float tmax) {
+    if (!rayTmax) return tmax;
+    const float t = rayTmax[ray];
+    return t != t ? __builtin_inff() : t;
+}
 
 // pt_trace_occluded on the binary LBVH (PT_KERNEL_SIMPLE / PT_KERNEL_WAVEFRONT): traceKernelQ's walk
 // (binStart / binVisit with ANY) with the interval fixed at the ray's tmax; a lane stops at the
@@ -2929,7 +2943,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_
         PT_TRACE_REFILL(took);
         if (__ballot(ray >= 0) == 0) break;
         if (ray < 0) continue;
-        if ((took && binStart<true>(S, rays[ray], tmin, rayTmax ? rayTmax[ray] : tmax, w, tmaxR, best, c)) ||
+        if ((took && binStart<true>(S, rays[ray], tmin, rayTmaxOf(rayTmax, ray, tmax), w, tmaxR, best, c)) ||
             binVisit<STACK, true>(S, my, tmin, w, tmaxR, best, c)) {
             occ[ray] = best >= 0 ? 1 : 0;
             ray = -1;
@@ -2966,7 +2980,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_
         if (ray < 0) continue;
         bool hit = false, fin = false;
         if (took) {
-            const float tmaxR = rayTmax ? rayTmax[ray] : tmax;
+            const float tmaxR = rayTmaxOf(rayTmax, ray, tmax);
             if (wideStart<INST>(S, rays[ray], tmin, tmaxR, w, tmaxI, c)) {   // the query in the reference's order: its flag
                 float closest = tmaxR;
                 hit = traceRefStackless(S, w.o, w.d, tmin, closest) >= 0;
@@ -4462,14 +4476,18 @@ int pt_scene_download_bvh(pt_scene* s, pt_bvh_node* out) {
     return PT_OK;
 }
 
-int pt_trace_closest(pt_scene* s, const pt_ray* rays, int64_t n, float tmin, float tmax, pt_hit* hits,
-                     pt_stats* stats) {
-    return pt_trace_closest_ex(s, rays, n, tmin, tmax, PT_KERNEL_DEFAULT, hits, stats);
-}
-
 }  // extern "C"
 
 namespace {
+// The ray queries' interval contract (include/pt.h, pt_trace_closest): tmin >= 0 and not NaN (-0.0
+// counts as 0), the scalar tmax not NaN; tmax < tmin is a legal, empty interval.  Checked by every
+// entry point before anything is allocated or launched.  (The kernels' accept tests rely on it:
+// `t >= 0.0f` with -1 as the miss marker.)
+int checkInterval(const char* who, float tmin, float tmax, bool scalarTmax = true) {
+    if (!(tmin >= 0.0f)) return fail(PT_ERR_INVALID, std::string(who) + ": tmin must be >= 0 and not NaN");
+    if (scalarTmax && std::isnan(tmax)) return fail(PT_ERR_INVALID, std::string(who) + ": tmax must not be NaN");
+    return PT_OK;
+}
 // A batch of n ray queries on device arrays, traced on `st`; the host waits for the end (counters
 // and the guard word are read back).  `who` prefixes the messages; defaultWide: PT_KERNEL_DEFAULT
 // is the wide tree (closest hit: for instanced scenes only; occlusion: always, the answer has no
@@ -4525,11 +4543,17 @@ int occludedDevice(pt_scene* s, const pt_ray* dr, int64_t n, float tmin, float t
 
 extern "C" {
 
+int pt_trace_closest(pt_scene* s, const pt_ray* rays, int64_t n, float tmin, float tmax, pt_hit* hits,
+                     pt_stats* stats) {
+    if (int rc = checkInterval("pt_trace_closest", tmin, tmax)) return rc;
+    return pt_trace_closest_ex(s, rays, n, tmin, tmax, PT_KERNEL_DEFAULT, hits, stats);
+}
+
 int pt_trace_closest_ex(pt_scene* s, const pt_ray* rays, int64_t n, float tmin, float tmax, int kernel, pt_hit* hits,
                         pt_stats* stats) {
     if (!s || n < 0 || (n > 0 && (!rays || !hits))) return fail(PT_ERR_INVALID, "pt_trace_closest: bad argument");
-    int rc = setDevice(s->device);
-    if (rc) return rc;
+    int rc = checkInterval("pt_trace_closest_ex", tmin, tmax);
+    if (rc || (rc = setDevice(s->device))) return rc;
     DevBuf dr, dh;
     if ((rc = devAlloc(dr, n * sizeof(pt_ray))) || (rc = devAlloc(dh, n * sizeof(pt_hit)))) return rc;
     if (n > 0) HIP_TRY(hipMemcpy(dr.p, rays, n * sizeof(pt_ray), hipMemcpyHostToDevice));
@@ -4541,14 +4565,15 @@ int pt_trace_closest_ex(pt_scene* s, const pt_ray* rays, int64_t n, float tmin, 
 int pt_trace_closest_device(pt_scene* s, const pt_ray* rays, int64_t n, float tmin, float tmax, int kernel,
                             pt_hit* hits, void* stream, pt_stats* stats) {
     if (!s || n < 0 || (n > 0 && (!rays || !hits))) return fail(PT_ERR_INVALID, "pt_trace_closest_device: bad argument");
+    if (int rc = checkInterval("pt_trace_closest_device", tmin, tmax)) return rc;
     return traceDevice(s, rays, n, tmin, tmax, kernel, hits, static_cast<hipStream_t>(stream), stats);
 }
 
 int pt_trace_occluded(pt_scene* s, const pt_ray* rays, int64_t n, float tmin, float tmax, const float* ray_tmax,
                       int kernel, uint8_t* occluded, pt_stats* stats) {
     if (!s || n < 0 || (n > 0 && (!rays || !occluded))) return fail(PT_ERR_INVALID, "pt_trace_occluded: bad argument");
-    int rc = setDevice(s->device);
-    if (rc) return rc;
+    int rc = checkInterval("pt_trace_occluded", tmin, tmax, !ray_tmax);
+    if (rc || (rc = setDevice(s->device))) return rc;
     DevBuf dr, dt, dq;
     if ((rc = devAlloc(dr, n * sizeof(pt_ray))) || (rc = devAlloc(dq, n))) return rc;
     if (ray_tmax && (rc = devAlloc(dt, n * sizeof(float)))) return rc;
@@ -4565,6 +4590,7 @@ int pt_trace_occluded_device(pt_scene* s, const pt_ray* rays, int64_t n, float t
                              int kernel, uint8_t* occluded, void* stream, pt_stats* stats) {
     if (!s || n < 0 || (n > 0 && (!rays || !occluded)))
         return fail(PT_ERR_INVALID, "pt_trace_occluded_device: bad argument");
+    if (int rc = checkInterval("pt_trace_occluded_device", tmin, tmax, !ray_tmax)) return rc;
     return occludedDevice(s, rays, n, tmin, tmax, ray_tmax, kernel, occluded, static_cast<hipStream_t>(stream), stats);
 }
 

@@ -77,7 +77,8 @@ __device__ __forceinline__ float fmaMixHi(uint32_t h2, float aS, float c) {
 // v_max3_f32 / v_min3_f32 on fmaMixHi results: an fmaxf / fminf on an asm output makes the compiler
 // quiet it first (one v_max_f32 x, x, x per operand: it cannot know the value is canonical).  The
 // plain instructions give the same result here (IEEE mode: a quiet NaN operand is ignored, the
-// fma results are never signalling).
+// fma results are never signalling, and neither are the interval bounds passed along with them: the
+// ray queries validate the scalars and read a NaN ray_tmax[i] as +inf, rayTmaxOf).
 __device__ __forceinline__ float max3Raw(float a, float b, float c) {
     float r;
     asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
