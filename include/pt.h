@@ -89,6 +89,48 @@ enum { PT_LAMBERTIAN = 1, PT_METAL = 2, PT_DIELECTRIC = 4, PT_EMISSIVE = 8 };
  *   and instanced scenes are PT_ERR_INVALID and nothing is rendered (instanced lights need world-space
  *   light records per instance). */
 #define PT_RENDER_NEE 4
+/* PT_RENDER_MIS (pt_render_opts.flags): next-event estimation with multiple importance sampling
+ * (balance heuristic) between the light sample and the Lambertian scatter ray.  It implies
+ * PT_RENDER_NEE, whether or not that bit is set.  G above is unbounded next to a light and only the
+ * clamp guards it; here both ways of reaching a sampled light -- the light sample, and the scatter ray
+ * that happens to land on it -- stay in the estimator, each weighted with its own pdf over the sum of
+ * the two, so every light term is bounded and the singular G is gone instead of clipped.  No new ray,
+ * no new draw.  Without the bit nothing changes (PT_RENDER_NEE frames included).
+ * Everything of the PT_RENDER_NEE rule stays: the light list, where the rule applies (a PT_LAMBERTIAN
+ * hit, after its scatter, bounces left, nL > 0), the draws uL, ua, ub, k, the fold and its two fminf,
+ * q, w, cs, cl, d2, the three rejections, the shadow ray over [0.001, 0.999), the counters, and the final
+ * fminf(direct + ending term, PT_MAX_RADIANCE) per sample.  Two things change.  Every operation is one
+ * rounded fp32 operation in the written order, dot and cross as above, sqrtf and / correctly rounded:
+ * The light sample's weight replaces G.  For an unoccluded sample:
+ *   len = sqrtf(d2)
+ *   pl  = ((2 * d2) * len) / ((float)nL * cl)      (the light sample's pdf per solid angle: 1 / nL, uniform
+ *                                                  on the triangle of area |cross(e1, e2)| / 2)
+ *   pb  = cs / (3.1415927f * len)                  (the Lambertian scatter's pdf of the same direction)
+ *   wl  = pb / (pl + pb)
+ *   direct += ((att * albedo) * E) * wl            per channel; a NaN channel counts as 0
+ *   ((albedo / pi) * E * cos / pl, the light sample's estimate, times its balance weight pl / (pl + pb).)
+ * The scatter ray carries its pdf.  At the same hit, whatever the rejections say, with n the hit's
+ *   normal and d the scatter ray's unnormalised direction:
+ *   pbs = fmaxf(dot(n, d), 0) / (3.1415927f * sqrtf(dot(d, d)))
+ * A sampled light hit by that scatter ray is weighted, not zeroed.  With t the hit's parameter and e1,
+ *   e2 the hit triangle's light-record edges:
+ *   wv  = t * d   (per component);   D2 = dot(wv, wv);   L = sqrtf(D2)
+ *   clh = |dot(cross(e1, e2), wv)|
+ *   pls = ((2 * D2) * L) / ((float)nL * clh)
+ *   wb  = pbs / (pls + pbs)
+ *   ending term = (att * E) * wb                   per channel; a NaN channel counts as 0
+ *   Every other emitter hit is as before, with weight 1: a primary hit, a hit after a metal or
+ *   dielectric scatter, any hit on an emissive sphere.
+ * Consequences: wl and wb lie in [0, 1] (pb, pbs >= 0 and pl, pls > 0 or NaN; a NaN weight's term is 0),
+ *   so every light term is at most (att * albedo) * E per channel, and no sample clamps in a scene
+ *   with max E / (1 - max Lambertian albedo) < PT_MAX_RADIANCE (both lit presets: 17 / 0.27).  The clamp
+ *   stays: the sample-mode accumulator's promise needs it whatever the scene.  A PT_RENDER_MIS frame
+ *   draws the same random numbers and traces the same rays as the PT_RENDER_NEE frame of the same
+ *   arguments: the streams, pt_stats.rays, paths and the work counters are identical, only the pixel
+ *   values differ.
+ * Scope: PT_RENDER_NEE's.  With the bit, PT_KERNEL_WAVEFRONT and instanced scenes are PT_ERR_INVALID
+ *   (the message names PT_RENDER_MIS) and nothing is rendered.  nL == 0: the bit changes nothing at all. */
+#define PT_RENDER_MIS 8
 
 /* One scene object, the reference's CudaObj (cuda_object.h:16-123) without device pointers.
  * sphere: v[0..2] = centre, v[3] = radius (negative radius = hollow sphere, as in RTIOW)
@@ -424,7 +466,8 @@ int pt_render(pt_scene* scene, pt_film* film, const pt_camera* cam, int spp, int
  *   accumulated samples per pixel.  (Sample mode's 32.32 fixed-point sums are exact while
  *   samples x radiance < 2^31: with emitters or a sky at PT_MAX_RADIANCE = 1024, 2^21 samples.)
  *   PT_RENDER_NEE: direct light sampling of the emissive triangles (the rule above, next to
- *   PT_EMISSIVE).  Any other bit is ignored.
+ *   PT_EMISSIVE).  PT_RENDER_MIS: the same with multiple importance sampling (implies
+ *   PT_RENDER_NEE; its rule follows that one).  Any other bit is ignored.
  * out_format: PT_OUT_RGB32F (3 floats per pixel), PT_OUT_RGBA8 (4 bytes per pixel, quantised on
  *   the device exactly like PngImage::saveColor, png_image.h:24-30: (uint8)(clamp(c,0,0.999)*256),
  *   alpha 255; rows in film order, row 0 = bottom, pt_write_png_rgba8 flips them) or

@@ -1009,8 +1009,15 @@ __device__ __forceinline__ float3 emitted(const HitRec& h, float3 att) {
 // sample of a Lambertian hit at p with normal n; att = the path's attenuation after the hit (the
 // attenuation before it times the albedo).  Draws uL, ua, ub whatever follows.  true: the shadow ray
 // (p, w) is to be traced, and `term` is what an unoccluded sample adds to the path.
+// MIS (PT_RENDER_MIS, pt.h): `term` carries the balance-heuristic weight wl in G's place.
 constexpr float kShadowTmax = 0.999f;   // the light sits at t = 1 of the unnormalised shadow ray
-template <class G>
+constexpr float kPi = 3.1415927f;
+// The light sample's pdf per solid angle of the direction of v (unnormalised, from the shaded point to
+// the light's plane): d2 = dot(v, v), cl = |dot(cross(e1, e2), v)|.
+__device__ __forceinline__ float lightPdf(float nLf, float d2, float cl) {
+    return ((2.0f * d2) * sqrtf(d2)) / (nLf * cl);   // (IEEE division and square root)
+}
+template <bool MIS = false, class G>
 __device__ __forceinline__ bool lightSample(const float4* __restrict__ lights, int nL, float3 p, float3 n, float3 att,
                                             G& g, float3& w, float3& term) {
     const float uL = g.uniform();
@@ -1029,7 +1036,14 @@ __device__ __forceinline__ bool lightSample(const float4* __restrict__ lights, i
     const float d2 = dot3(w, w);
     term = f3(0.0f, 0.0f, 0.0f);
     if (cs <= 0.0f || cl == 0.0f || d2 == 0.0f) return false;
-    const float G_ = ((cs * cl) * nLf) / (6.2831855f * (d2 * d2));   // (IEEE division)
+    float G_;
+    if constexpr (MIS) {   // wl = pb / (pl + pb): the scatter's pdf of this direction over the two pdfs' sum
+        const float pl = lightPdf(nLf, d2, cl);
+        const float pb = cs / (kPi * sqrtf(d2));
+        G_ = pb / (pl + pb);
+    } else {
+        G_ = ((cs * cl) * nLf) / (6.2831855f * (d2 * d2));   // (IEEE division)
+    }
     const float3 t = scale(G_, mul(att, E));
     term = f3(t.x != t.x ? 0.0f : t.x, t.y != t.y ? 0.0f : t.y, t.z != t.z ? 0.0f : t.z);
     return true;
@@ -1037,6 +1051,25 @@ __device__ __forceinline__ bool lightSample(const float4* __restrict__ lights, i
 // The hit on shading record k is a sampled light: an emissive triangle (not an emissive sphere).
 __device__ __forceinline__ bool sampledLight(const float4* shade, int k, const HitRec& h) {
     return h.type == PT_EMISSIVE && (__float_as_uint(shade[3 * (size_t)k + 2].y) >> 16) == 0u;
+}
+// PT_RENDER_MIS: the Lambertian scatter's pdf per solid angle of its own ray's direction d (unnormalised),
+// taken at the hit where the rule applies ...
+__device__ __forceinline__ float scatterPdf(float3 n, float3 d) {
+    return fmaxf(dot3(n, d), 0.0f) / (kPi * sqrtf(dot3(d, d)));
+}
+// ... and the ending term of that ray when it lands on the sampled light `obj` (object index; slot[obj] =
+// its light record) at parameter t: att * E weighted with wb = pbs / (pls + pbs), pls = the light
+// sample's pdf of the same direction, from the hit's own t * d.
+__device__ __forceinline__ float3 emittedWeighted(const float4* __restrict__ lights, const uint32_t* __restrict__ slot,
+                                                  int nL, int obj, float t, float3 d, float pbs, float3 attE) {
+    const float4* L = lights + 4 * (size_t)slot[obj];
+    const float3 e1 = xyz(L[1]), e2 = xyz(L[2]);
+    const float3 wv = scale(t, d);
+    const float D2 = dot3(wv, wv);
+    const float clh = fabsf(dot3(cross3(e1, e2), wv));
+    const float wb = pbs / (lightPdf((float)nL, D2, clh) + pbs);
+    const float3 c = scale(wb, attE);
+    return f3(c.x != c.x ? 0.0f : c.x, c.y != c.y ? 0.0f : c.y, c.z != c.z ? 0.0f : c.z);
 }
 // A finished sample under NEE: the direct terms plus the path's ending term, clamped per channel.
 __device__ __forceinline__ float3 neeTotal(float3 direct, float3 contrib) {
@@ -1109,6 +1142,10 @@ struct RenderParams {
     // last build and their count nL > 0 (the kernels' NEE instantiations); 0: the rule is off.
     const float4* lights;
     int nLights;
+    // PT_RENDER_MIS (with nLights > 0; the kernels' MIS instantiations): object index -> slot in
+    // `lights` (the build's scan; read for hits on sampled lights only), and the flag.
+    int mis;
+    const uint32_t* lightSlot;
 };
 template <bool LIT>
 __device__ __forceinline__ float3 skyOf(const RenderParams& P, float3 d, float3 att) {
@@ -1215,8 +1252,10 @@ __device__ __forceinline__ void lensOffset(float3 right, float3 up, float lens, 
 
 // NEE (with LIT): next-event estimation as a nested query -- the shadow ray is traced where the
 // Lambertian hit is shaded, then the loop goes on with the scatter ray.
-template <int STACK, bool SAMPLE, bool LIT = false, bool NEE = false>
+// MIS (with NEE): the light sample's and the scatter ray's weights (PT_RENDER_MIS, pt.h).
+template <int STACK, bool SAMPLE, bool LIT = false, bool NEE = false, bool MIS = false>
 __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
+    static_assert(!MIS || NEE, "MIS: the NEE instantiations only");
     __shared__ uint32_t stk[STACK * kWave];
     const int lane = threadIdx.x;
     const int tile = tileOf(P, blockIdx.x);
@@ -1239,6 +1278,7 @@ __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
         int depthLeft = 0, sample = 0;
         float3 direct = f3(0.0f, 0.0f, 0.0f);   // NEE: the path's direct terms so far
         bool fromNee = false;                    // NEE: the current ray left a hit where the rule applied
+        float pbs = 0.0f;                        // MIS: that ray's scatter pdf
         // newPath: main.cu:284-286 + camera::get_ray (camera.h:58-64): the lens sample from the
         // path's stream (lensOffset), the time draw skipped (no moving objects on the path).
         auto newPath = [&]() {
@@ -1293,7 +1333,11 @@ __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
                     if (!scatter(P.S, h, d, na, g)) {
                         contrib = LIT ? emitted(h, att) : f3(0.0f, 0.0f, 0.0f);
                         if constexpr (NEE) {   // the light was sampled at the hit this ray left
-                            if (fromNee && sampledLight(P.S.shade, k, h)) contrib = f3(0.0f, 0.0f, 0.0f);
+                            if (fromNee && sampledLight(P.S.shade, k, h)) {
+                                if constexpr (MIS)
+                                    contrib = emittedWeighted(P.lights, P.lightSlot, P.nLights, h.obj, closest, d, pbs, contrib);
+                                else contrib = f3(0.0f, 0.0f, 0.0f);
+                            }
                         }
                         done = true;
                     } else {
@@ -1304,7 +1348,8 @@ __global__ __launch_bounds__(kWave) void renderKernel(RenderParams P) {
                             fromNee = h.type == PT_LAMBERTIAN;
                             if (fromNee) {
                                 float3 w, term;
-                                if (lightSample(P.lights, P.nLights, o, h.n, att, g, w, term)) {
+                                if constexpr (MIS) pbs = scatterPdf(h.n, d);
+                                if (lightSample<MIS>(P.lights, P.nLights, o, h.n, att, g, w, term)) {
                                     c.rays++;
                                     float tS = kShadowTmax;
                                     if (trace<STACK>(P.S, o, w, 0.001f, tS, my, c) < 0) direct = add(direct, term);
@@ -1457,12 +1502,16 @@ __device__ __forceinline__ float3 skyK(float3 d, float3 att) {
 // samples a light parks the scatter direction and the pending direct term in LDS and begins the
 // shadow ray from the hit point; the SHADE step that finds that query complete adds the term when
 // nothing was hit and begins the parked scatter ray.  NODE and LEAF steps do not know the difference.
-template <int STACK, bool SAMPLE, bool WIDE, bool INST = false, bool LIT = false, bool NEE = false>
+// MIS (with NEE): the weights of PT_RENDER_MIS (pt.h).  One more float of lane state, the scatter
+// ray's pdf, beside the parked direction in LDS: written by the SHADE step that scatters, read by the
+// SHADE step that finds that ray on a sampled light.
+template <int STACK, bool SAMPLE, bool WIDE, bool INST = false, bool LIT = false, bool NEE = false, bool MIS = false>
 // (NEE on the deeper wide stacks, 16 and 24 entries: 4 waves per SIMD instead of 5 -- at 96 VGPRs the
 // SHADE step's light sample spilled 1-3 registers, and the 24-entry stack's 6 KB of LDS with the
 // 2.5 KB of NEE state fit 4 waves anyway)
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPerEU<STACK, SAMPLE, WIDE> - (NEE && STACK >= 16 ? 1 : 0)))) void renderKernelWF(RenderParams P) {
     static_assert(!NEE || (WIDE && LIT && !INST), "NEE: the flat wide kernels' LIT instantiations only");
+    static_assert(!MIS || NEE, "MIS: the NEE instantiations only");
     // Deep trees (binary kernels) keep 32 stack entries per lane in LDS (8 KB per wave: 5 waves
     // per SIMD) and the rare deeper entries in global memory (stackSpill, per wave slot and lane).
     constexpr int LS = kLdsStack<STACK, SAMPLE, WIDE>;
@@ -1483,8 +1532,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     // parked scatter direction [6..8] of a shadow query, and two flag bits -- 1: the lane's current
     // query is a shadow ray, 2: its scatter ray leaves a hit where the rule applied (a sampled light
     // it lands on contributes nothing).  Like taskState, touched by SHADE steps only: LDS, not VGPRs
-    // carried through every NODE and LEAF step.
-    __shared__ float neeV[NEE ? 9 * kWave : 1];
+    // carried through every NODE and LEAF step.  MIS: [9] the scatter ray's pdf (pbs).
+    __shared__ float neeV[NEE ? (MIS ? 10 : 9) * kWave : 1];
     __shared__ uint32_t neeF[NEE ? kWave : 1];
     const int lane = threadIdx.x;
     // compat mode: all spp of a pixel in order (its per-pixel XORWOW stream); one wave = one tile
@@ -2217,8 +2266,12 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                     if (!scatterInto(h, d, att, g)) {
                         if constexpr (LIT) contrib = emitted(h, att);
                         if constexpr (NEE) {   // the light was sampled at the hit this ray left
-                            if ((nf & 2u) && sampledLight(kargs()->S.wshade, best & (int)kPrimMask, h))
-                                contrib = f3(0.0f, 0.0f, 0.0f);
+                            if ((nf & 2u) && sampledLight(kargs()->S.wshade, best & (int)kPrimMask, h)) {
+                                if constexpr (MIS)
+                                    contrib = emittedWeighted(kargs()->lights, kargs()->lightSlot, kargs()->nLights, h.obj,
+                                                              closest, d, neeV[9 * kWave + lane], contrib);
+                                else contrib = f3(0.0f, 0.0f, 0.0f);
+                            }
                         }
                         done = true;
                     } else {
@@ -2229,7 +2282,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                             if (h.type == PT_LAMBERTIAN) {
                                 nf |= 2u;
                                 float3 w, term;
-                                if (lightSample(kargs()->lights, kargs()->nLights, o, h.n, att, g, w, term)) {
+                                if constexpr (MIS) neeV[9 * kWave + lane] = scatterPdf(h.n, d);
+                                if (lightSample<MIS>(kargs()->lights, kargs()->nLights, o, h.n, att, g, w, term)) {
                                     neeV[3 * kWave + lane] = term.x; neeV[4 * kWave + lane] = term.y; neeV[5 * kWave + lane] = term.z;
                                     neeV[6 * kWave + lane] = d.x; neeV[7 * kWave + lane] = d.y; neeV[8 * kWave + lane] = d.z;
                                     d = w;
@@ -2370,7 +2424,8 @@ int launchCompatWide(int stack, const void* params, hipStream_t st) {
     switch (stack) {
 #define PT_COMPAT_WIDE(S)                                                                    \
         case S:                                                                                  \
-            if (P.nLights > 0) renderKernelWF<S, false, true, false, true, true><<<grid, kWave, 0, st>>>(P); \
+            if (P.nLights > 0 && P.mis) renderKernelWF<S, false, true, false, true, true, true><<<grid, kWave, 0, st>>>(P); \
+            else if (P.nLights > 0) renderKernelWF<S, false, true, false, true, true><<<grid, kWave, 0, st>>>(P); \
             else if (P.lit) renderKernelWF<S, false, true, false, true><<<grid, kWave, 0, st>>>(P); \
             else renderKernelWF<S, false, true><<<grid, kWave, 0, st>>>(P);                      \
             break;
@@ -3836,7 +3891,8 @@ void launchRenderWide(const RenderParams& P, hipStream_t st) {
     if (P.pixAcc) {
         if constexpr (LIT) {   // (NEE launches are LIT: a sampled light is an emissive material)
             if (P.nLights > 0) {
-                renderKernelWF<S, true, true, false, true, true><<<P.nwaves, kWave, 0, st>>>(P);
+                if (P.mis) renderKernelWF<S, true, true, false, true, true, true><<<P.nwaves, kWave, 0, st>>>(P);
+                else renderKernelWF<S, true, true, false, true, true><<<P.nwaves, kWave, 0, st>>>(P);
                 return;
             }
         }
@@ -3851,6 +3907,8 @@ void launchRender(const RenderParams& P, hipStream_t st) {
         renderKernelWF<S, true, false, false, LIT><<<P.nwaves, kWave, 0, st>>>(P);
     else if (P.kernel == PT_KERNEL_WAVEFRONT)
         renderKernelWF<S, false, false, false, LIT><<<P.compatGrid, kWave, 0, st>>>(P);
+    else if (LIT && P.nLights > 0 && P.mis && P.pixAcc) renderKernel<S, true, LIT, LIT, LIT><<<P.ntiles, kWave, 0, st>>>(P);
+    else if (LIT && P.nLights > 0 && P.mis) renderKernel<S, false, LIT, LIT, LIT><<<P.ntiles, kWave, 0, st>>>(P);
     else if (LIT && P.nLights > 0 && P.pixAcc) renderKernel<S, true, LIT, LIT><<<P.ntiles, kWave, 0, st>>>(P);
     else if (LIT && P.nLights > 0) renderKernel<S, false, LIT, LIT><<<P.ntiles, kWave, 0, st>>>(P);
     else if (P.pixAcc) renderKernel<S, true, LIT><<<P.ntiles, kWave, 0, st>>>(P);
@@ -3879,14 +3937,15 @@ bool withBinStack(int stack, F f) { return withStack<16, 24, 32, 48, 64, 80>(sta
 // the same LDS and waves-per-SIMD attribute, so the same occupancy (DESIGN.md's resource table).
 // The compat wide kernels live in pt_compat.hip's
 // translation unit.
-int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, bool nee) {
+int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, bool nee, bool mis) {
     const bool wide = kernel == PT_KERNEL_WIDE;
-    if (wide && !inst && sample && nee) {   // the NEE kernels hold more LDS per wave: asked of themselves
+    if (wide && !inst && sample && nee) {   // the NEE and MIS kernels hold more LDS per wave: asked of themselves
         int rc = PT_OK;
         const bool ok = withWideStack(stack, [&](auto N) {
             constexpr int K = decltype(N)::value;
             const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &n, reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true>), kWave, 0);
+                &n, mis ? reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true, true>)
+                        : reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true>), kWave, 0);
             if (e != hipSuccess) rc = fail(PT_ERR_HIP, std::string("hipOccupancyMaxActiveBlocksPerMultiprocessor: ") + hipGetErrorString(e));
         });
         if (!ok) return fail(PT_ERR_STATE, "unsupported wide BVH depth");
@@ -4704,7 +4763,8 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     if (fmt != PT_OUT_RGB32F && fmt != PT_OUT_RGBA8 && fmt != PT_OUT_RGBA8_SURFACE)
         return fail(PT_ERR_INVALID, "pt_render_ex: unknown output format");
     const bool accumulate = opts && (opts->flags & PT_RENDER_ACCUMULATE);
-    const bool neeFlag = opts && (opts->flags & PT_RENDER_NEE);
+    const bool misFlag = opts && (opts->flags & PT_RENDER_MIS);   // (implies PT_RENDER_NEE)
+    const bool neeFlag = misFlag || (opts && (opts->flags & PT_RENDER_NEE));
     const size_t outBpp = fmt == PT_OUT_RGB32F ? 12 : 4;
     if (accumulate && f->accumSamples + spp >= (1ll << 24))
         return fail(PT_ERR_INVALID, "pt_render_ex: accumulated samples must stay below 2^24");
@@ -4720,12 +4780,18 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
         return fail(PT_ERR_INVALID, "pt_render_ex: unknown kernel");
     if (s->instanced && kernel != PT_KERNEL_WIDE)
         return fail(PT_ERR_INVALID, "pt_render_ex: instanced scenes render with the wide kernel (PT_KERNEL_WIDE)");
+    if (misFlag && s->instanced)
+        return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_MIS is not available on instanced scenes (flat scenes only)");
+    if (misFlag && kernel == PT_KERNEL_WAVEFRONT)
+        return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_MIS is not available with PT_KERNEL_WAVEFRONT "
+                                    "(PT_KERNEL_WIDE, PT_KERNEL_DEFAULT or PT_KERNEL_SIMPLE)");
     if (neeFlag && s->instanced)
         return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_NEE is not available on instanced scenes (flat scenes only)");
     if (neeFlag && kernel == PT_KERNEL_WAVEFRONT)
         return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_NEE is not available with PT_KERNEL_WAVEFRONT "
                                     "(PT_KERNEL_WIDE, PT_KERNEL_DEFAULT or PT_KERNEL_SIMPLE)");
     const bool nee = neeFlag && s->nLights > 0;   // (no sampled light: the flag changes nothing)
+    const bool mis = misFlag && nee;
     const int rng = opts ? opts->rng : PT_RNG_COMPAT;
     if (rng != PT_RNG_COMPAT && rng != PT_RNG_SAMPLE) return fail(PT_ERR_INVALID, "pt_render_ex: unknown rng mode");
     if (kernel == PT_KERNEL_WIDE && (rc = ensureWide(s))) return rc;   // (first use: builds the tree)
@@ -4766,6 +4832,8 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     }
     P.lights = nee ? s->lights.as<float4>() : nullptr;
     P.nLights = nee ? (int)s->nLights : 0;
+    P.mis = mis ? 1 : 0;
+    P.lightSlot = mis ? s->lightSlot.as<uint32_t>() : nullptr;
     uint32_t* b = f->state.as<uint32_t>();
     P.sd = b; P.s0 = b + np; P.s1 = b + 2 * np; P.s2 = b + 3 * np; P.s3 = b + 4 * np; P.s4 = b + 5 * np;
     P.out = static_cast<float*>(dst);
@@ -4861,16 +4929,16 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     // occupancy per CU, which the LDS stack caps on deep trees.  Queried once per (device, kernel
     // instantiation) and process.
     auto perCUFor = [&](int& perCU) -> int {
-        static std::atomic<int> cached[16][2][2][2][3][2];   // [device][sample][instanced][wide][stack 8, 16, 24][nee]
+        static std::atomic<int> cached[16][2][2][2][3][3];   // [device][sample][instanced][wide][stack 8, 16, 24][blind, nee, mis]
         const bool small = stack <= 24 && stack % 8 == 0 && f->device >= 0 && f->device < 16;
         std::atomic<int>* c = small ? &cached[f->device][sample ? 1 : 0][s->instanced ? 1 : 0]
-                                             [kernel == PT_KERNEL_WIDE ? 1 : 0][stack / 8 - 1][nee ? 1 : 0] : nullptr;
+                                             [kernel == PT_KERNEL_WIDE ? 1 : 0][stack / 8 - 1][mis ? 2 : nee ? 1 : 0] : nullptr;
         const int known = c ? c->load(std::memory_order_relaxed) : 0;
         if (known > 0) {
             perCU = known;
             return PT_OK;
         }
-        if (int r = persistentWavesPerCU(stack, kernel, perCU, s->instanced, sample, nee)) return r;
+        if (int r = persistentWavesPerCU(stack, kernel, perCU, s->instanced, sample, nee, mis)) return r;
         if (c) c->store(perCU, std::memory_order_relaxed);
         return PT_OK;
     };

@@ -17,13 +17,16 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: pt_render_png [--scene NAME] [--models DIR] [--width W] [--height H] [--spp N]\n"
                  "                     [--depth D] [--seed S] [--gpus N] [--stripe ROWS] [--out FILE]\n"
-                 "                     [--rng compat|sample] [--frames K] [--sky default|black] [--nee]\n"
+                 "                     [--rng compat|sample] [--frames K] [--sky default|black] [--nee] [--mis]\n"
                  "--frames K: progressive rendering, K frames of --spp samples accumulated per pixel (the\n"
                  "            headless counterpart of the reference's interactive loop); PNG of the last one\n"
                  "--sky: the sky the scene is rendered under; without it the preset's own (pt_preset_sky):\n"
                  "       black for the _lit scenes, whose lamp emits, the reference's gradient otherwise\n"
                  "--nee: next-event estimation (PT_RENDER_NEE): sample the emissive triangles directly at every\n"
                  "       Lambertian hit; off by default; changes nothing in a scene without emissive triangles\n"
+                 "--mis: next-event estimation with multiple importance sampling (PT_RENDER_MIS; implies --nee):\n"
+                 "       the light sample and the scatter ray weighted by their pdfs (balance heuristic), so the\n"
+                 "       light term next to a lamp is bounded instead of clamped\n"
                  "scenes: triangle_world (default, as the reference), random_world, test_world, rtiow,\n"
                  "        cornell, bunny_cornell, bunny_field, cornell_lit, bunny_cornell_lit\n");
 }
@@ -40,7 +43,7 @@ static void usage() {
 int main(int argc, char** argv) {
     std::string scene = "triangle_world", models = "models", out = "debug.png", sky;
     int width = 0, height = 0, spp = -1, depth = -1, gpus = 1, stripe = 8, frames = 1, rng = PT_RNG_COMPAT;
-    bool nee = false;
+    bool nee = false, mis = false;
     unsigned long long seed = 1;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -60,6 +63,7 @@ int main(int argc, char** argv) {
         else if (a == "--out") out = next();
         else if (a == "--frames") frames = std::atoi(next());
         else if (a == "--nee") nee = true;
+        else if (a == "--mis") mis = true;
         else if (a == "--sky") {
             sky = next();
             if (sky != "default" && sky != "black") { usage(); return 2; }
@@ -113,7 +117,7 @@ int main(int argc, char** argv) {
             pt_render_opts o{};
             o.rng = rng;
             o.out_format = PT_OUT_RGBA8;
-            o.flags = (frames > 1 ? PT_RENDER_ACCUMULATE : 0) | (nee ? PT_RENDER_NEE : 0);
+            o.flags = (frames > 1 ? PT_RENDER_ACCUMULATE : 0) | (nee ? PT_RENDER_NEE : 0) | (mis ? PT_RENDER_MIS : 0);
             pt_stats st{};
             for (int k = 0; k < frames; k++) {
                 CHECK(pt_render_ex(s, f, &d.camera, d.spp, d.max_depth, reinterpret_cast<float*>(part.data()), 0,

@@ -59,6 +59,7 @@ class RenderOpts(C.Structure):
 RNG_COMPAT, RNG_SAMPLE = 0, 1
 IDENTITY_ORDER, ACCUMULATE = 1, 2
 NEE = 4   # PT_RENDER_NEE: next-event estimation (direct sampling of the emissive triangles)
+MIS = 8   # PT_RENDER_MIS: the same with multiple importance sampling (balance heuristic); implies NEE
 OUT_RGB32F, OUT_RGBA8, OUT_RGBA8_SURFACE = 0, 1, 2
 
 
@@ -533,13 +534,16 @@ class Film:
 def render(scene: Scene, film: Film, camera: Camera, spp: int, max_depth: int, out=None, stream=None,
            kernel: int = KERNEL_DEFAULT, leaf_batch: int = 0, shade_batch: int = 0, rng: int = RNG_COMPAT,
            chunk: int = 0, flags: int = 0, accumulate: bool = False, out_format: int = OUT_RGB32F,
-           wait: bool = True, nee: bool = False):
+           wait: bool = True, nee: bool = False, mis: bool = False):
     """Render spp samples per pixel of the film's rows.  `out` may be a numpy array (host) or
     an integer device pointer (then `stream` is a hipStream_t handle or None).  Returns
     (rgb or None, Stats); rgb is float32 (n_pixels, 3), or uint8 (n_pixels, 4) for the 8-bit
     output formats.  accumulate=True adds the frame to the film's running sums (progressive).
     nee=True sets PT_RENDER_NEE: direct light sampling of the scene's emissive triangles (pt.h states
     the rule; flat scenes, the wide and simple kernels; nothing changes when scene.n_lights == 0).
+    mis=True sets PT_RENDER_MIS: the same with the light sample and the scatter ray weighted by the
+    balance heuristic (bounded light terms: no clamp bias next to a lamp); it implies nee, traces the
+    same rays and draws the same random numbers as the nee=True frame.
     wait=False (device output only): the frame is enqueued and the call returns at once with
     Stats None -- film.stats() waits for it and returns its counters."""
     st = Stats()
@@ -547,6 +551,8 @@ def render(scene: Scene, film: Film, camera: Camera, spp: int, max_depth: int, o
         flags |= ACCUMULATE
     if nee:
         flags |= NEE
+    if mis:
+        flags |= MIS
     opts = RenderOpts(kernel, leaf_batch, shade_batch, flags, rng, chunk, out_format, 0)
     if out is None or isinstance(out, np.ndarray):
         if out is None:
