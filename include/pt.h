@@ -84,10 +84,27 @@ enum { PT_LAMBERTIAN = 1, PT_METAL = 2, PT_DIELECTRIC = 4, PT_EMISSIVE = 8 };
  * Clamp: a finished sample contributes fminf(direct + ending term, PT_MAX_RADIANCE) per channel (one
  *   add, one fminf).  G is unbounded near a light; the clamp keeps the sample-mode accumulator exact
  *   while N * PT_MAX_RADIANCE < 2^31 and is the rule's one deliberate bias.
- * Scope: flat scenes, PT_KERNEL_WIDE / PT_KERNEL_DEFAULT and PT_KERNEL_SIMPLE, both RNG modes, with
- *   PT_RENDER_ACCUMULATE, partitioned films and every output format.  With the flag, PT_KERNEL_WAVEFRONT
- *   and instanced scenes are PT_ERR_INVALID and nothing is rendered (instanced lights need world-space
- *   light records per instance). */
+ * Instanced scenes list their lights on request: pt_scene_build_bvh* with PT_BVH_LIGHTS (below).
+ *   Lights: the (instance, object) pairs whose object is a PT_TRIANGLE with a PT_EMISSIVE material, in
+ *   flattened object order (instances in order, each contributing its mesh's emissive triangles in
+ *   object order); nL is their number and does not depend on the matrices.  Each vertex (x, y, z) of
+ *   the triangle goes to the world through the instance's matrix m in fp64: row r gives
+ *   w_r = ((m[r][0] * x + m[r][1] * y) + m[r][2] * z) + m[r][3], m, x, y, z converted to double, one
+ *   rounded fp64 operation each in that order, no contraction; w_r is rounded to fp32 once.  Then
+ *   e1 = v1' - v0' and e2 = v2' - v0' in fp32 of the rounded vertices, and E is the material's albedo.
+ *   An identity matrix therefore gives the flat scene's record bit for bit.  Emission is two-sided and
+ *   cl an absolute value, so a mirrored instance (det < 0) needs no special case.  Everything else of
+ *   the rule is unchanged: p and n are the instanced hit's world-space point and normal; "a sampled
+ *   light" hit by a scatter ray is an emissive triangle of any instance; the shadow ray is an instanced
+ *   closest-hit query over the same interval, which like every instanced result equals the flattened
+ *   scene's within the documented tolerance (bit for bit for identity instances).  The records follow
+ *   pt_scene_update_instances: every build with the bit writes them from the current matrices with the
+ *   same device code, the top-level-only rebuild included (no allocation there either), so a rebuilt
+ *   scene's list is a fresh scene's bit for bit.  64 B per record.
+ * Scope: PT_KERNEL_WIDE / PT_KERNEL_DEFAULT on flat scenes and on instanced scenes whose last build
+ *   had PT_BVH_LIGHTS, PT_KERNEL_SIMPLE on flat scenes; both RNG modes, with PT_RENDER_ACCUMULATE,
+ *   partitioned films and every output format.  With the flag, PT_KERNEL_WAVEFRONT and an instanced
+ *   scene whose last build did not have PT_BVH_LIGHTS are PT_ERR_INVALID and nothing is rendered. */
 #define PT_RENDER_NEE 4
 /* PT_RENDER_MIS (pt_render_opts.flags): next-event estimation with multiple importance sampling
  * (balance heuristic) between the light sample and the Lambertian scatter ray.  It implies
@@ -128,8 +145,11 @@ enum { PT_LAMBERTIAN = 1, PT_METAL = 2, PT_DIELECTRIC = 4, PT_EMISSIVE = 8 };
  *   draws the same random numbers and traces the same rays as the PT_RENDER_NEE frame of the same
  *   arguments: the streams, pt_stats.rays, paths and the work counters are identical, only the pixel
  *   values differ.
- * Scope: PT_RENDER_NEE's.  With the bit, PT_KERNEL_WAVEFRONT and instanced scenes are PT_ERR_INVALID
- *   (the message names PT_RENDER_MIS) and nothing is rendered.  nL == 0: the bit changes nothing at all. */
+ * Instanced scenes built with PT_BVH_LIGHTS: the light list is PT_RENDER_NEE's; e1, e2 of a sampled
+ *   light hit by the scatter ray are those of the hit (instance, triangle)'s own record.
+ * Scope: PT_RENDER_NEE's.  With the bit, PT_KERNEL_WAVEFRONT and an instanced scene whose last build did
+ *   not have PT_BVH_LIGHTS are PT_ERR_INVALID (the message names PT_RENDER_MIS) and nothing is rendered.
+ *   nL == 0: the bit changes nothing at all. */
 #define PT_RENDER_MIS 8
 
 /* One scene object, the reference's CudaObj (cuda_object.h:16-123) without device pointers.
@@ -271,6 +291,15 @@ int pt_scene_set_sky(pt_scene* scene, const float horizon[3], const float zenith
  * same images.  On an instanced scene the flag means "lay the scene out for instance updates"
  * (pt_scene_update_instances). */
 #define PT_BVH_WIDE_DEVICE 4
+/* PT_BVH_LIGHTS: on an instanced scene, list the sampled lights of PT_RENDER_NEE / PT_RENDER_MIS in
+ * world space, one 64-byte record per (instance, emissive triangle of its mesh) -- the rule is stated
+ * at PT_RENDER_NEE.  Opt-in, because a scene that never samples lights should not pay for the list.
+ * The bit holds for that build only: a later build without it lists none (pt_scene_light_count is 0
+ * again and the render flags are refused as before).  It composes with PT_BVH_WIDE_DEVICE: the
+ * top-level-only rebuild after pt_scene_update_instances writes the list from tables the full build
+ * made, without allocating; when the last full build did not have the bit, the first build that asks for
+ * it is the full one.  On a flat scene it is ignored: flat builds list their lights as ever. */
+#define PT_BVH_LIGHTS 8
 int pt_scene_build_bvh(pt_scene* scene, int flags);
 /* pt_scene_build_bvh with its device work enqueued on `stream` (a hipStream_t, NULL = the null
  * stream) instead of the null stream; returns when the build is complete (the tree depth is read
@@ -332,8 +361,14 @@ int pt_scene_update_objects(pt_scene* scene, const pt_object* objs, int64_t firs
  * those are found then depends on the boxes entered, in any two builds of a scene.  A scene that was never updated builds exactly as before. */
 int pt_scene_update_instances(pt_scene* scene, const pt_instance* instances, int64_t first, int64_t n);
 /* nL, the number of sampled lights (PT_RENDER_NEE: the emissive triangles) the last build listed;
- * 0 for an instanced scene.  PT_ERR_STATE before a build, or after an update that made it stale. */
+ * 0 for an instanced scene built without PT_BVH_LIGHTS.  PT_ERR_STATE before a build, or after an update
+ * that made it stale. */
 int pt_scene_light_count(pt_scene* scene, int64_t* n);
+/* The light records of the last build, flat or instanced: nL x 12 floats, {v0, e1, e2, E} of each record
+ * in list order, as the kernels read them.  PT_ERR_INVALID for a NULL scene, PT_ERR_STATE before a build
+ * or on a stale scene; nL == 0 writes nothing and is PT_OK; a NULL `records` with nL > 0 is
+ * PT_ERR_INVALID. */
+int pt_scene_download_lights(pt_scene* scene, float* records);
 /* Device time of the last pt_scene_build_bvh (HIP events around the build's stream work). */
 int pt_scene_build_time(pt_scene* scene, double* ms);
 int pt_scene_bvh_info(pt_scene* scene, int* depth, int64_t* n_nodes, int64_t* device_bytes);

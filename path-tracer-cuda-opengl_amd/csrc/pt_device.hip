@@ -1060,9 +1060,9 @@ __device__ __forceinline__ float scatterPdf(float3 n, float3 d) {
 // ... and the ending term of that ray when it lands on the sampled light `obj` (object index; slot[obj] =
 // its light record) at parameter t: att * E weighted with wb = pbs / (pls + pbs), pls = the light
 // sample's pdf of the same direction, from the hit's own t * d.
-__device__ __forceinline__ float3 emittedWeighted(const float4* __restrict__ lights, const uint32_t* __restrict__ slot,
-                                                  int nL, int obj, float t, float3 d, float pbs, float3 attE) {
-    const float4* L = lights + 4 * (size_t)slot[obj];
+__device__ __forceinline__ float3 emittedWeightedAt(const float4* __restrict__ lights, uint32_t rec, int nL, float t, float3 d,
+                                                    float pbs, float3 attE) {
+    const float4* L = lights + 4 * (size_t)rec;
     const float3 e1 = xyz(L[1]), e2 = xyz(L[2]);
     const float3 wv = scale(t, d);
     const float D2 = dot3(wv, wv);
@@ -1070,6 +1070,16 @@ __device__ __forceinline__ float3 emittedWeighted(const float4* __restrict__ lig
     const float wb = pbs / (lightPdf((float)nL, D2, clh) + pbs);
     const float3 c = scale(wb, attE);
     return f3(c.x != c.x ? 0.0f : c.x, c.y != c.y ? 0.0f : c.y, c.z != c.z ? 0.0f : c.z);
+}
+__device__ __forceinline__ float3 emittedWeighted(const float4* __restrict__ lights, const uint32_t* __restrict__ slot,
+                                                  int nL, int obj, float t, float3 d, float pbs, float3 attE) {
+    return emittedWeightedAt(lights, slot[obj], nL, t, d, pbs, attE);
+}
+// An instanced scene's record of hit key `key` (instance << gBits | shading index): the instance's first
+// record plus the rank of the object among its mesh's sampled lights (instLightKernel's order).
+__device__ __forceinline__ uint32_t instLightSlot(const uint32_t* __restrict__ instFirst, const uint32_t* __restrict__ rank,
+                                                  uint32_t key, int gBits) {
+    return instFirst[key >> gBits] + rank[key & ((1u << gBits) - 1u)];
 }
 // A finished sample under NEE: the direct terms plus the path's ending term, clamped per channel.
 __device__ __forceinline__ float3 neeTotal(float3 direct, float3 contrib) {
@@ -1146,6 +1156,9 @@ struct RenderParams {
     // `lights` (the build's scan; read for hits on sampled lights only), and the flag.
     int mis;
     const uint32_t* lightSlot;
+    // Instanced scenes built with PT_BVH_LIGHTS: lightSlot is indexed by shading index and holds the
+    // object's rank among its mesh's sampled lights; instLightFirst: the first record of each instance.
+    const uint32_t* instLightFirst;
 };
 template <bool LIT>
 __device__ __forceinline__ float3 skyOf(const RenderParams& P, float3 d, float3 att) {
@@ -1497,7 +1510,7 @@ __device__ __forceinline__ float3 skyK(float3 d, float3 att) {
 // group would belong to another space), no reference-order redo (instanced frames are held to a
 // tolerance, not bit for bit).
 // LIT: scenes with an emissive material or a sky of their own (RenderParams::lit).
-// NEE (with WIDE, LIT, not INST): next-event estimation (PT_RENDER_NEE, pt.h).  A shadow ray is an
+// NEE (with WIDE, LIT): next-event estimation (PT_RENDER_NEE, pt.h).  A shadow ray is an
 // ordinary query of the step machine whose `closest` starts at kShadowTmax: the SHADE step that
 // samples a light parks the scatter direction and the pending direct term in LDS and begins the
 // shadow ray from the hit point; the SHADE step that finds that query complete adds the term when
@@ -1505,12 +1518,15 @@ __device__ __forceinline__ float3 skyK(float3 d, float3 att) {
 // MIS (with NEE): the weights of PT_RENDER_MIS (pt.h).  One more float of lane state, the scatter
 // ray's pdf, beside the parked direction in LDS: written by the SHADE step that scatters, read by the
 // SHADE step that finds that ray on a sampled light.
+// NEE with INST (scenes built with PT_BVH_LIGHTS): the light records are world-space, one per (instance,
+// emissive triangle); a SHADE step finds its lane back in the world (the marker was popped), so the
+// shadow ray and the parked scatter ray start there like any bounce.
 template <int STACK, bool SAMPLE, bool WIDE, bool INST = false, bool LIT = false, bool NEE = false, bool MIS = false>
 // (NEE on the deeper wide stacks, 16 and 24 entries: 4 waves per SIMD instead of 5 -- at 96 VGPRs the
 // SHADE step's light sample spilled 1-3 registers, and the 24-entry stack's 6 KB of LDS with the
 // 2.5 KB of NEE state fit 4 waves anyway)
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPerEU<STACK, SAMPLE, WIDE> - (NEE && STACK >= 16 ? 1 : 0)))) void renderKernelWF(RenderParams P) {
-    static_assert(!NEE || (WIDE && LIT && !INST), "NEE: the flat wide kernels' LIT instantiations only");
+    static_assert(!NEE || (WIDE && LIT), "NEE: the wide kernels' LIT instantiations only");
     static_assert(!MIS || NEE, "MIS: the NEE instantiations only");
     // Deep trees (binary kernels) keep 32 stack entries per lane in LDS (8 KB per wave: 5 waves
     // per SIMD) and the rare deeper entries in global memory (stackSpill, per wave slot and lane).
@@ -1674,7 +1690,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 ng = 0u;       /* origin far from the scene, or a direction the MIX planes */      \
                 oct |= 8u;     /* cannot take: the query in the reference's order (SHADE's redo) */ \
             }                                                                                     \
-            if (INST && kargs()->camFar && depthLeft + 1 == kargs()->max_depth) {                  \
+            if (INST && kargs()->camFar && !sh_ && depthLeft + 1 == kargs()->max_depth) {          \
                 /* a far camera: the path starts where its ray enters the world (instEntry) */     \
                 const auto& K_ = *kargs();                                                        \
                 (void)instEntry(K_.S.cx, K_.S.cy, K_.S.cz, K_.S.ext, o, d, inv);                   \
@@ -2266,8 +2282,15 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                     if (!scatterInto(h, d, att, g)) {
                         if constexpr (LIT) contrib = emitted(h, att);
                         if constexpr (NEE) {   // the light was sampled at the hit this ray left
-                            if ((nf & 2u) && sampledLight(kargs()->S.wshade, best & (int)kPrimMask, h)) {
-                                if constexpr (MIS)
+                            // (instanced: the hit key's low gBits bits are the shading index)
+                            const int sk = INST ? best & ((1 << kargs()->S.gBits) - 1) : best & (int)kPrimMask;
+                            if ((nf & 2u) && sampledLight(kargs()->S.wshade, sk, h)) {
+                                if constexpr (MIS && INST)
+                                    contrib = emittedWeightedAt(kargs()->lights,
+                                                                instLightSlot(kargs()->instLightFirst, kargs()->lightSlot,
+                                                                              (uint32_t)best & kPrimMask, kargs()->S.gBits),
+                                                                kargs()->nLights, closest, d, neeV[9 * kWave + lane], contrib);
+                                else if constexpr (MIS)
                                     contrib = emittedWeighted(kargs()->lights, kargs()->lightSlot, kargs()->nLights, h.obj,
                                                               closest, d, neeV[9 * kWave + lane], contrib);
                                 else contrib = f3(0.0f, 0.0f, 0.0f);
@@ -3588,6 +3611,16 @@ struct pt_scene {
     DevBuf instPrims, instRank, instEntriesDev, instMeshRootDev, instWprims, instErr;
     EventPair instEvents;                   // the later builds' timing events, created once
     std::vector<float> instHostM;           // their staging buffers, kept between builds
+    // Sampled lights of an instanced scene (PT_BVH_LIGHTS; pt.h states the rule): one world-space record
+    // per (instance, emissive triangle of its mesh) in `lights`, written by pt::instanceLights on every
+    // build that has the bit.  The tables depend on the meshes only and are made by the full build: the
+    // emissive triangles' object indices mesh by mesh (instLightObj), per instance where its mesh's run
+    // starts there (instLightSrc) and its first record (instLightFirst, n + 1 entries), and in
+    // `lightSlot` each shading record's rank among its mesh's lights (the MIS kernels' lookup).
+    bool instLights = false;                // the last build had PT_BVH_LIGHTS
+    bool instLightsPrepared = false;        // the tables and the record buffer match the meshes
+    int64_t instLightTotal = 0;             // records: fixed under pt_scene_update_instances
+    DevBuf instLightFirst, instLightSrc, instLightObj;
     std::vector<double> instHostBox;
 };
 
@@ -3718,11 +3751,58 @@ pt::InstancedIn instancedIn(const pt_scene* s) {
     return in;
 }
 
+// PT_BVH_LIGHTS, the full build's part: the per-mesh tables (host: a pass over the objects) and every
+// buffer the light list needs, so that the later builds allocate nothing.
+int prepareInstanceLights(pt_scene* s) {
+    s->instLightsPrepared = false;
+    const size_t nm = s->meshFirst.size(), ni = s->inst.size();
+    std::vector<uint32_t> obj, rank, meshSrc(nm), meshN(nm), first(ni + 1), src(std::max<size_t>(1, ni));
+    for (size_t m = 0; m < nm; m++) {
+        meshSrc[m] = (uint32_t)obj.size();
+        for (int64_t k = 0; k < s->meshCount[m]; k++) {
+            const pt_object& o = s->objs[(size_t)(s->meshFirst[m] + k)];
+            const bool light = s->hasEmissive && o.type == PT_TRIANGLE && s->matEmissive[(size_t)o.mat];
+            rank.push_back(light ? (uint32_t)obj.size() - meshSrc[m] : 0u);   // (shading index order: mesh by mesh)
+            if (light) obj.push_back((uint32_t)(s->meshFirst[m] + k));
+        }
+        meshN[m] = (uint32_t)obj.size() - meshSrc[m];
+    }
+    int64_t total = 0;
+    for (size_t i = 0; i < ni; i++) {
+        first[i] = (uint32_t)total;
+        src[i] = meshSrc[(size_t)s->inst[i].mesh];
+        total += meshN[(size_t)s->inst[i].mesh];
+        if (total > (int64_t)1 << 26) return fail(PT_ERR_INVALID, "pt_scene_build_bvh: PT_BVH_LIGHTS: more than 2^26 light records");
+    }
+    first[ni] = (uint32_t)total;
+    s->instLightTotal = total;
+    if (total > 0) {
+        struct Upload { DevBuf* buf; const void* src; size_t bytes; };
+        const Upload up[] = {{&s->instLightFirst, first.data(), first.size() * 4}, {&s->instLightSrc, src.data(), src.size() * 4},
+                             {&s->instLightObj, obj.data(), obj.size() * 4}, {&s->lightSlot, rank.data(), rank.size() * 4},
+                             {&s->lights, nullptr, (size_t)total * 4 * sizeof(float4)}, {&s->instM, nullptr, ni * 48}};
+        for (const Upload& u : up) {
+            if (int rc = devReserve(*u.buf, u.bytes)) return rc;
+            if (u.src) HIP_TRY(hipMemcpy(u.buf->p, u.src, u.bytes, hipMemcpyHostToDevice));
+        }
+    }
+    s->instLightsPrepared = true;
+    return PT_OK;
+}
+// Every build with the bit: the records from the matrices in instM, on `st` (csrc/pt_inst_build.hip).
+hipError_t enqueueInstanceLights(pt_scene* s, hipStream_t st) {
+    const pt::InstLightIn in{s->dobjs.as<pt_object>(), s->mats.as<float>(), s->instM.as<float>(),
+                             s->instLightFirst.as<uint32_t>(), s->instLightSrc.as<uint32_t>(), s->instLightObj.as<uint32_t>(),
+                             (uint32_t)s->inst.size(), (uint32_t)s->instLightTotal};
+    return pt::instanceLights(in, s->lights.as<float4>(), st);
+}
+
 // The full build: pt::buildInstancedTree on the scene's host copies (the materials come back from
 // the device in the layout the shading records inline), the arrays uploaded, the scene committed.
-int buildInstanced(pt_scene* s) {
+int buildInstanced(pt_scene* s, bool lights, hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
     s->instPrepared = false;
+    s->instLightsPrepared = false;
     std::vector<float> mats((size_t)std::max<int64_t>(1, 2 * s->nmat) * 4);
     HIP_TRY(hipMemcpy(mats.data(), s->mats.p, mats.size() * 4, hipMemcpyDeviceToHost));
     pt::InstancedIn in = instancedIn(s);
@@ -3771,6 +3851,20 @@ int buildInstanced(pt_scene* s) {
         s->instMaxDepthB = t.maxDepthB;
         s->instPrepared = true;
     }
+    if (lights) {   // (the tables first: the later builds find every buffer in place)
+        if ((rc = prepareInstanceLights(s))) return rc;
+        if (s->instLightTotal > 0) {
+            std::vector<float> hm(s->inst.size() * 12);
+            for (size_t i = 0; i < s->inst.size(); i++) std::memcpy(&hm[i * 12], s->inst[i].m, 48);
+            HIP_TRY(hipMemcpy(s->instM.p, hm.data(), hm.size() * 4, hipMemcpyHostToDevice));
+            StreamWait guard(st);
+            HIP_TRY(enqueueInstanceLights(s, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            guard.ok = true;
+        }
+    }
+    s->instLights = lights;
+    s->nLights = lights ? s->instLightTotal : 0;
     s->wideBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     s->buildMs = s->wideBuildMs;
     s->depth = 0;
@@ -3790,7 +3884,7 @@ int buildInstanced(pt_scene* s) {
 // the build has succeeded.
 // *done = false (and PT_OK): a mesh's new reach exceeds the reach its tree was quantised for --
 // the caller runs the full build.
-int rebuildInstancedTop(pt_scene* s, hipStream_t st, bool* done) {
+int rebuildInstancedTop(pt_scene* s, bool lights, hipStream_t st, bool* done) {
     const auto t0 = std::chrono::steady_clock::now();
     *done = false;
     const int64_t ni = (int64_t)s->inst.size();
@@ -3849,6 +3943,8 @@ int rebuildInstancedTop(pt_scene* s, hipStream_t st, bool* done) {
     HIP_TRY(pt::instanceRecords(s->wide.as<uint32_t>(), (uint32_t)topSlots, s->instWprims.as<uint32_t>(),
                                 s->instEntriesDev.as<uint32_t>(), (uint32_t)ne, s->winst.as<float>(),
                                 s->instMeshRootDev.as<uint32_t>(), s->instErr.as<uint32_t>(), st));
+    // PT_BVH_LIGHTS: the light records of the new matrices (the full build's kernel and tables)
+    if (lights && s->instLightTotal > 0) HIP_TRY(enqueueInstanceLights(s, st));
     uint32_t bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, s->instErr.p, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(ev.e1, st));
@@ -3862,6 +3958,8 @@ int rebuildInstancedTop(pt_scene* s, hipStream_t st, bool* done) {
     s->wideDepth = topDepth + 1 + s->instMaxDepthB + 1;
     s->wideSource = 4;
     s->wideReady = true;
+    s->instLights = lights;
+    s->nLights = lights ? s->instLightTotal : 0;
     s->buildMs = (double)ms;
     s->wideBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     s->depth = 0;
@@ -3884,6 +3982,15 @@ int setDevice(int dev) {
 template <int S, bool LIT>
 void launchRenderWide(const RenderParams& P, hipStream_t st) {
     if (P.S.winst) {   // an instanced scene's two-level tree
+        if constexpr (LIT) {   // (built with PT_BVH_LIGHTS: the NEE / MIS kernels, as below)
+            if (P.nLights > 0) {
+                if (P.pixAcc && P.mis) renderKernelWF<S, true, true, true, true, true, true><<<P.nwaves, kWave, 0, st>>>(P);
+                else if (P.pixAcc) renderKernelWF<S, true, true, true, true, true><<<P.nwaves, kWave, 0, st>>>(P);
+                else if (P.mis) renderKernelWF<S, false, true, true, true, true, true><<<P.compatGrid, kWave, 0, st>>>(P);
+                else renderKernelWF<S, false, true, true, true, true><<<P.compatGrid, kWave, 0, st>>>(P);
+                return;
+            }
+        }
         if (P.pixAcc) renderKernelWF<S, true, true, true, LIT><<<P.nwaves, kWave, 0, st>>>(P);
         else renderKernelWF<S, false, true, true, LIT><<<P.compatGrid, kWave, 0, st>>>(P);
         return;
@@ -3939,13 +4046,15 @@ bool withBinStack(int stack, F f) { return withStack<16, 24, 32, 48, 64, 80>(sta
 // translation unit.
 int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, bool nee, bool mis) {
     const bool wide = kernel == PT_KERNEL_WIDE;
-    if (wide && !inst && sample && nee) {   // the NEE and MIS kernels hold more LDS per wave: asked of themselves
+    if (wide && sample && nee) {   // the NEE and MIS kernels hold more LDS per wave: asked of themselves
         int rc = PT_OK;
         const bool ok = withWideStack(stack, [&](auto N) {
             constexpr int K = decltype(N)::value;
-            const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &n, mis ? reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true, true>)
-                        : reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true>), kWave, 0);
+            const void* k = inst ? (mis ? reinterpret_cast<const void*>(&renderKernelWF<K, true, true, true, true, true, true>)
+                                        : reinterpret_cast<const void*>(&renderKernelWF<K, true, true, true, true, true>))
+                                 : (mis ? reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true, true>)
+                                        : reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true>));
+            const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, kWave, 0);
             if (e != hipSuccess) rc = fail(PT_ERR_HIP, std::string("hipOccupancyMaxActiveBlocksPerMultiprocessor: ") + hipGetErrorString(e));
         });
         if (!ok) return fail(PT_ERR_STATE, "unsupported wide BVH depth");
@@ -4269,12 +4378,15 @@ int pt_scene_build_bvh_ex(pt_scene* s, int flags, void* stream) {
         // is the full host build in that layout; later ones redo the matrix-dependent work alone,
         // unless a mesh's reach has outgrown its tree (then the full build again).
         if (flags & PT_BVH_WIDE_DEVICE) s->instDynamic = true;
-        if (s->instDynamic && s->instPrepared) {
+        // PT_BVH_LIGHTS: the sampled lights in world space, for this build; the later builds write them
+        // from the tables of a full build that had the bit.
+        const bool lights = (flags & PT_BVH_LIGHTS) != 0;
+        if (s->instDynamic && s->instPrepared && (!lights || s->instLightsPrepared)) {
             bool done = false;
-            if ((rc = rebuildInstancedTop(s, static_cast<hipStream_t>(stream), &done))) return rc;
+            if ((rc = rebuildInstancedTop(s, lights, static_cast<hipStream_t>(stream), &done))) return rc;
             if (done) return PT_OK;
         }
-        return buildInstanced(s);
+        return buildInstanced(s, lights, static_cast<hipStream_t>(stream));
     }
     const int64_t n = s->nobj;
     s->built = false;
@@ -4462,6 +4574,21 @@ int pt_scene_light_count(pt_scene* s, int64_t* n) {
     if (!s || !n) return fail(PT_ERR_INVALID, "pt_scene_light_count: null argument");
     if (!s->built) return fail(PT_ERR_STATE, "pt_scene_light_count: BVH not built");
     *n = s->nLights;
+    return PT_OK;
+}
+
+int pt_scene_download_lights(pt_scene* s, float* records) {
+    if (!s) return fail(PT_ERR_INVALID, "pt_scene_download_lights: null scene");
+    if (!s->built) return fail(PT_ERR_STATE, "pt_scene_download_lights: BVH not built");
+    const int64_t n = s->nLights;
+    if (n == 0) return PT_OK;
+    if (!records) return fail(PT_ERR_INVALID, "pt_scene_download_lights: null records");
+    int rc = setDevice(s->device);
+    if (rc) return rc;
+    std::vector<float> rec((size_t)n * 16);
+    HIP_TRY(hipMemcpy(rec.data(), s->lights.p, rec.size() * 4, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; i++)
+        for (int v = 0; v < 4; v++) std::memcpy(records + 12 * i + 3 * v, &rec[(size_t)(16 * i + 4 * v)], 12);
     return PT_OK;
 }
 
@@ -4780,12 +4907,12 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
         return fail(PT_ERR_INVALID, "pt_render_ex: unknown kernel");
     if (s->instanced && kernel != PT_KERNEL_WIDE)
         return fail(PT_ERR_INVALID, "pt_render_ex: instanced scenes render with the wide kernel (PT_KERNEL_WIDE)");
-    if (misFlag && s->instanced)
+    if (misFlag && s->instanced && !s->instLights)   // (an instanced scene lists its lights on request: PT_BVH_LIGHTS)
         return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_MIS is not available on instanced scenes (flat scenes only)");
     if (misFlag && kernel == PT_KERNEL_WAVEFRONT)
         return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_MIS is not available with PT_KERNEL_WAVEFRONT "
                                     "(PT_KERNEL_WIDE, PT_KERNEL_DEFAULT or PT_KERNEL_SIMPLE)");
-    if (neeFlag && s->instanced)
+    if (neeFlag && s->instanced && !s->instLights)
         return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_NEE is not available on instanced scenes (flat scenes only)");
     if (neeFlag && kernel == PT_KERNEL_WAVEFRONT)
         return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_NEE is not available with PT_KERNEL_WAVEFRONT "
@@ -4833,7 +4960,8 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     P.lights = nee ? s->lights.as<float4>() : nullptr;
     P.nLights = nee ? (int)s->nLights : 0;
     P.mis = mis ? 1 : 0;
-    P.lightSlot = mis ? s->lightSlot.as<uint32_t>() : nullptr;
+    P.lightSlot = mis ? s->lightSlot.as<uint32_t>() : nullptr;   // (instanced: the ranks by shading index)
+    P.instLightFirst = mis && s->instanced ? s->instLightFirst.as<uint32_t>() : nullptr;
     uint32_t* b = f->state.as<uint32_t>();
     P.sd = b; P.s0 = b + np; P.s1 = b + 2 * np; P.s2 = b + 3 * np; P.s3 = b + 4 * np; P.s4 = b + 5 * np;
     P.out = static_cast<float*>(dst);

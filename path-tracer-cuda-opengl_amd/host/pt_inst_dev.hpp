@@ -37,4 +37,17 @@ hipError_t instanceBoxes(const InstBoxIn& in, double* ibox, float* ebox, hipStre
 hipError_t instanceRecords(uint32_t* nodes, uint32_t slots, const uint32_t* wprims, const uint32_t* entries, uint32_t nEntries,
                            const float* winst, const uint32_t* meshRoot, uint32_t* err, hipStream_t stream);
 
+// The sampled lights of an instanced scene built with PT_BVH_LIGHTS (pt.h: the rule): nLights records
+// {v0}{e1}{e2}{E} of 4 float4, one per (instance, emissive triangle of its mesh), in world space.
+struct InstLightIn {
+    const pt_object* objs;    // the scene's objects (object space)
+    const float* mats;        // the device's material records, 8 floats each (the albedo slot first: E)
+    const float* m;           // nInst x 12: the instances' matrices
+    const uint32_t* first;    // nInst + 1: each instance's first record; first[nInst] = nLights
+    const uint32_t* src;      // nInst: where the instance's mesh's run starts in `obj`
+    const uint32_t* obj;      // the emissive triangles' object indices, mesh by mesh, in object order
+    uint32_t nInst, nLights;
+};
+hipError_t instanceLights(const InstLightIn& in, float4* lights, hipStream_t stream);
+
 }  // namespace pt

@@ -23,6 +23,7 @@ PT_SPHERE, PT_TRIANGLE = 1, 3
 PT_LAMBERTIAN, PT_METAL, PT_DIELECTRIC, PT_EMISSIVE = 1, 2, 4, 8
 PT_MAX_RADIANCE = 1024.0   # bound of an emissive material's radiance and of the sky colours
 PT_BVH_ORIGIN_BOUNDS, PT_BVH_HOST_KEYS, PT_BVH_WIDE_DEVICE = 1, 2, 4
+PT_BVH_LIGHTS = 8   # instanced scenes: list the sampled lights in world space (render(nee=True / mis=True))
 
 # numpy mirrors of the C structs (all 4-byte fields, no padding)
 OBJECT_DTYPE = np.dtype([("type", "<i4"), ("mat", "<i4"), ("v", "<f4", (9,))])
@@ -95,6 +96,7 @@ EXPORTS = [
     "pt_scene_build_bvh_ex", "pt_film_stats", "pt_preset_instanced", "pt_instanced_desc_free",
     "pt_scene_create_instanced", "pt_trace_occluded", "pt_trace_occluded_device",
     "pt_scene_update_instances", "pt_scene_set_sky", "pt_preset_sky", "pt_scene_light_count",
+    "pt_scene_download_lights",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -135,6 +137,7 @@ _sig = {
     "pt_film_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "pt_scene_build_time": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "pt_scene_light_count": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "pt_scene_download_lights": (C.c_int, [_P, _P]),
     "pt_scene_update_objects": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
     "pt_scene_update_instances": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
     "pt_scene_bvh_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -324,9 +327,11 @@ class Scene:
 
     @classmethod
     def instanced(cls, objects: np.ndarray, mesh_first, mesh_count, instances: np.ndarray, materials: np.ndarray,
-                  device: int = 0, build: bool = True) -> "Scene":
+                  device: int = 0, build: bool = True, flags: int = 0) -> "Scene":
         """pt_scene_create_instanced: each mesh stored once (object space), placed by `instances`
-        (INSTANCE_DTYPE); rendered and traced by the wide kernel over a two-level tree."""
+        (INSTANCE_DTYPE); rendered and traced by the wide kernel over a two-level tree.  flags: the
+        first build's (PT_BVH_WIDE_DEVICE: laid out for update_instances; PT_BVH_LIGHTS: the sampled
+        lights listed in world space, for render(nee=True / mis=True))."""
         self = cls.__new__(cls)
         self.objects = np.ascontiguousarray(objects, OBJECT_DTYPE)
         self.materials = np.ascontiguousarray(materials, MATERIAL_DTYPE)
@@ -345,7 +350,7 @@ class Scene:
             "pt_scene_create_instanced")
         self.h = h
         if build:
-            self.build_bvh()
+            self.build_bvh(flags)
         return self
 
     def build_bvh(self, flags: int = PT_BVH_ORIGIN_BOUNDS, stream=None) -> None:
@@ -389,6 +394,13 @@ class Scene:
         n = C.c_int64()
         _check(lib.pt_scene_light_count(self.h, C.byref(n)), "pt_scene_light_count")
         return n.value
+
+    def lights(self) -> np.ndarray:
+        """pt_scene_download_lights: the last build's light records as (n_lights, 4, 3) float32,
+        {v0, e1, e2, E} each, in list order (an instanced scene: built with PT_BVH_LIGHTS)."""
+        rec = np.zeros((self.n_lights, 4, 3), np.float32)
+        _check(lib.pt_scene_download_lights(self.h, _ptr(rec) if len(rec) else None), "pt_scene_download_lights")
+        return rec
 
     @property
     def build_ms(self) -> float:
@@ -540,7 +552,8 @@ def render(scene: Scene, film: Film, camera: Camera, spp: int, max_depth: int, o
     (rgb or None, Stats); rgb is float32 (n_pixels, 3), or uint8 (n_pixels, 4) for the 8-bit
     output formats.  accumulate=True adds the frame to the film's running sums (progressive).
     nee=True sets PT_RENDER_NEE: direct light sampling of the scene's emissive triangles (pt.h states
-    the rule; flat scenes, the wide and simple kernels; nothing changes when scene.n_lights == 0).
+    the rule; flat scenes on the wide and simple kernels, instanced scenes built with PT_BVH_LIGHTS on
+    the wide kernel; nothing changes when scene.n_lights == 0).
     mis=True sets PT_RENDER_MIS: the same with the light sample and the scatter ray weighted by the
     balance heuristic (bounded light terms: no clamp bias next to a lamp); it implies nee, traces the
     same rays and draws the same random numbers as the nee=True frame.

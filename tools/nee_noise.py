@@ -16,8 +16,11 @@ For each scene, at a reduced frame, in sample mode with the default (wide) kerne
 The reference's own noise (RMSE of a blind frame scales as spp^-1/2, so it is sqrt(spp / ref_spp) of a
 rung's blind RMSE) is in every figure, and so is the clamp's bias in the NEE rows; neither is removed.
 
+With --instanced the same ladder runs on the instanced form of each preset (pt_preset_instanced), built
+with PT_BVH_LIGHTS: the instanced NEE / MIS kernels, reference and blind rungs instanced too.
+
 usage: nee_noise.py [--scenes cornell_lit,bunny_cornell_lit] [--size 512] [--ref-spp 65536]
-                    [--ladder 16,64,256,1024] [--repeat 3] [--split SPP] [--json FILE]
+                    [--ladder 16,64,256,1024] [--repeat 3] [--split SPP] [--instanced] [--json FILE]
 (Smaller frames or rungs are not throughput-bound: a 256 x 256 frame at 4 spp is one launch's overhead.)
 Prints a Markdown table per scene and, with --json, writes every figure.
 """
@@ -41,6 +44,7 @@ ap.add_argument("--ref-spp", type=int, default=65536)
 ap.add_argument("--ladder", default="16,64,256,1024")
 ap.add_argument("--repeat", type=int, default=3)
 ap.add_argument("--split", type=int, default=0)
+ap.add_argument("--instanced", action="store_true")
 ap.add_argument("--json")
 a = ap.parse_args()
 ladder = [int(x) for x in a.ladder.split(",")]
@@ -74,10 +78,15 @@ def blind_rmse_at(t, rungs):
     raise AssertionError
 
 
-out = {"size": a.size, "ref_spp": a.ref_spp, "ladder": ladder, "scenes": {}}
+out = {"size": a.size, "ref_spp": a.ref_spp, "ladder": ladder, "instanced": a.instanced, "scenes": {}}
 for name in a.scenes.split(","):
-    p = ptamd.Preset(name, a.size, a.size)
-    scene = ptamd.Scene(p.objects, p.materials)
+    if a.instanced:
+        p = ptamd.InstancedPreset(name, a.size, a.size)
+        scene = ptamd.Scene.instanced(p.objects, p.mesh_first, p.mesh_count, p.instances, p.materials,
+                                      flags=ptamd.PT_BVH_LIGHTS)
+    else:
+        p = ptamd.Preset(name, a.size, a.size)
+        scene = ptamd.Scene(p.objects, p.materials)
     scene.set_sky(*p.sky)
     ref, ref_ms, _ = frame(scene, p, 1, a.ref_spp, "blind", 0)
     rows = {m: [] for m in MODES}
@@ -92,7 +101,7 @@ for name in a.scenes.split(","):
         r["ratio"] = r["blind_rmse_at_equal_time"] / r["rmse"]
     out["scenes"][name] = {"lights": scene.n_lights, "max_depth": p.max_depth, "reference_ms": ref_ms,
                            "reference_mean": float(ref.mean()), **rows}
-    print(f"\n{name}, {a.size} x {a.size}, depth {p.max_depth}, {scene.n_lights} sampled lights; reference: blind, "
+    print(f"\n{name}{' (instanced)' if a.instanced else ''}, {a.size} x {a.size}, depth {p.max_depth}, {scene.n_lights} sampled lights; reference: blind, "
           f"{a.ref_spp} spp ({ref_ms:.0f} ms), mean {ref.mean():.4f}\n")
     print("| spp | blind RMSE | blind ms | NEE RMSE | NEE ms | blind RMSE at the NEE frame's time | ratio "
           "| MIS RMSE | MIS ms | blind RMSE at the MIS frame's time | ratio |")
