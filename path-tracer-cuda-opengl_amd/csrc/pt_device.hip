@@ -537,25 +537,33 @@ __device__ __forceinline__ uint32_t wideHits(uint4 n0, uint4 n1, uint4 n2, uint4
     const float bx = (__uint_as_float(n0.x) - o.x) * inv.x;
     const float by = (__uint_as_float(n0.y) - o.y) * inv.y;
     const float bz = (__uint_as_float(n0.z) - o.z) * inv.z;
-    // near / far planes per axis: qlo for a positive direction, qhi for a negative one
-    const bool sx = (oct & 1u) != 0, sy = (oct & 2u) != 0, sz = (oct & 4u) != 0;
+    // near / far planes per axis: qlo for a positive direction, qhi for a negative one.  The signs
+    // are read off inv itself: `oct` is (inv.x < 0) | (inv.y < 0) << 1 | (inv.z < 0) << 2 wherever it
+    // is set, in the same statement as inv or right behind it (PT_BEGIN_RAY, wideStart; instanced
+    // scenes recompute both on entering an instance whose matrix turns the direction and on leaving
+    // it, and keep both otherwise), so these are oct's bits, NaN included (false both ways) -- as
+    // compares of values the step holds anyway, not three masks and three integer compares of oct.
+    const bool sx = inv.x < 0.0f, sy = inv.y < 0.0f, sz = inv.z < 0.0f;
     const uint32_t nearX[2] = {sx ? n2.z : n2.x, sx ? n2.w : n2.y}, farX[2] = {sx ? n2.x : n2.z, sx ? n2.y : n2.w};
     const uint32_t nearY[2] = {sy ? n3.z : n3.x, sy ? n3.w : n3.y}, farY[2] = {sy ? n3.x : n3.z, sy ? n3.y : n3.w};
     const uint32_t nearZ[2] = {sz ? n4.z : n4.x, sz ? n4.w : n4.y}, farZ[2] = {sz ? n4.x : n4.z, sz ? n4.y : n4.w};
-    // the octant in every byte (shifts: the multiply by 0x01010101 is a quarter-rate v_mul_lo_u32)
-    const uint32_t oct2 = oct | shlOpaque<8>(oct);
-    const uint32_t oct4 = oct2 | (oct2 << 16);
     uint32_t hits = 0u;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const uint32_t meta4 = h ? n1.w : n1.z;
         // per byte: internal children (0b001_11xxx) get their slot bits XOR the ray octant
-        const uint32_t inner4 = (meta4 & (meta4 << 1)) & 0x10101010u;
-        // 0x07 in the bytes of internal children (oct4 <= 0x07070707): 8y - y, not a multiply
+        // (bits 4 and 3 of the byte, and the mask, in one three-input AND)
+        const uint32_t inner4 = __builtin_amdgcn_bitop3_b32(meta4, meta4 << 1, 0x10101010u, 0x80);
+        // the octant in the bytes of internal children: 0x01 per such byte times oct (<= 7, no carry
+        // between bytes) as one packed 16-bit multiply (pt_math.hpp mulHalves) -- full rate, where the
+        // 32-bit v_mul_lo_u32 is quarter rate.  (Every caller passes the bare octant: `oct & 7u` or WideWalk::oct.)
         const uint32_t inner1 = inner4 >> 4;
-        const uint32_t innerMask4 = shlOpaque<3>(inner1) - inner1;
-        const uint32_t bitIndex4 = (meta4 ^ (oct4 & innerMask4)) & 0x1f1f1f1fu;
-        const uint32_t childBits4 = (meta4 >> 5) & 0x07070707u;
+        const uint32_t bitIndex4 = (meta4 ^ mulHalves(inner1, oct)) & 0x1f1f1f1fu;
+        // The counts as a word of their own the compiler cannot trace back to meta4: each child's
+        // `byte of childBits4 << byte of bitIndex4` below is then ONE shift with both byte selects
+        // (SDWA), where a count taken from meta4 directly is a v_bfe_u32 per child first.
+        uint32_t childBits4 = (meta4 >> 5) & 0x07070707u;
+        asm("" : "+v"(childBits4));
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             float tnx, tny, tnz, tfx, tfy, tfz;

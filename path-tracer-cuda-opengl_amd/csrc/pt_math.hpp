@@ -89,6 +89,13 @@ __device__ __forceinline__ float min3Raw(float a, float b, float c) {
     asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+// Both 16-bit halves of a2 times the low half of b (v_pk_mul_lo_u16, op_sel_hi picks b's low half for
+// the high lane too): wideHits multiplies a 0x01-per-byte flag word by the ray octant with it.
+__device__ __forceinline__ uint32_t mulHalves(uint32_t a2, uint32_t b) {
+    uint32_t r;
+    asm("v_pk_mul_lo_u16 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(a2), "v"(b));
+    return r;
+}
 // Sample mode: a block's fp32 sum as a 32.32 fixed-point integer (truncated toward zero; NaN -> 0,
 // saturated at +-2^62), and back (oracle/pt_oracle.cpp blockFixed / fixedToFloat, same roundings).
 // (Truncation done as two 32-bit halves of |p|: a * 2^-32 and a - hi * 2^32 are exact, hi has at

@@ -16,6 +16,10 @@ grouped into regions: the helper function that contains them, or -- inside rende
 its code runs (iterations per step kind from a PT_ITER_STATS run, loop trips), which
 DESIGN.md section 11 works out next to this table.
 
+The s_nop / waitcnt / `v_mov v,v` columns count the wait states the hazard recogniser filled, the
+waits on memory counters, and plain register-to-register copies (`v_mov_b32 vN, vM`: phi copies the
+register coalescer could not remove).
+
 The last column counts lane masks rebuilt through a VGPR inside one basic block (`v_cndmask_b32 v,
 0, 1, mask` followed by `v_cmp_ne_u32 .., 0, v`): what a `__ballot` of a predicate that is no plain
 compare costs (section 11 item 13).
@@ -91,7 +95,7 @@ def source_regions():
 
 def main() -> None:
     asm = sys.argv[1] if len(sys.argv) > 1 else "/tmp/isa/pt_device_g.s"
-    want = sys.argv[2] if len(sys.argv) > 2 else "renderKernelWFILi8ELb1ELb1ELb0E"
+    want = sys.argv[2] if len(sys.argv) > 2 else "renderKernelWFILi8ELb1ELb1ELb0ELb0ELb0ELb0E"
     text = open(asm).read().split("\n")
     files = {}
     start = None
@@ -154,6 +158,16 @@ def main() -> None:
                 last = r
             per_region[r or last][c] += 1
             per_line[key][c] += 1
+            # wait states the hazard recogniser filled, waits on memory counters, and plain
+            # register-to-register copies (phi copies the coalescer could not remove)
+            if ins.startswith("s_nop"):
+                per_region[r or last]["nop"] += 1
+                total["s_nop"] += 1
+            elif ins.startswith("s_waitcnt"):
+                per_region[r or last]["waitcnt"] += 1
+            elif re.match(r"v_mov_b32_e32 v\d+, v\d+$", ins):
+                per_region[r or last]["mov"] += 1
+                total["v_mov v,v"] += 1
             # a lane mask rebuilt through a VGPR: v_cndmask_b32 v, 0, 1, s[m] then v_cmp_ne_u32 .., 0, v
             # (a __ballot of a predicate that is no plain compare; two VALU for a mask that exists)
             m = re.match(r"v_cndmask_b32_e64 (v\d+), 0, 1, (s\[|vcc)", ins)
@@ -166,9 +180,9 @@ def main() -> None:
                 del rebuilt[m2.group(1)]
         prev = last
     print(f"kernel {want}: " + ", ".join(f"{k} {v}" for k, v in total.most_common()))
-    print(f"{'region':40s} {'VALU':>6s} {'SALU':>6s} {'VMEM':>5s} {'LDS':>4s} {'br':>4s} {'mask rebuilds':>14s}")
+    print(f"{'region':40s} {'VALU':>6s} {'SALU':>6s} {'VMEM':>5s} {'LDS':>4s} {'br':>4s} {'s_nop':>6s} {'waitcnt':>8s} {'v_mov v,v':>10s} {'mask rebuilds':>14s}")
     for reg, c in sorted(per_region.items(), key=lambda kv: -kv[1]["valu"]):
-        print(f"{reg:40s} {c['valu']:6d} {c['salu']:6d} {c['vmem']:5d} {c['lds']:4d} {c['branch']:4d} {c['rebuild']:14d}")
+        print(f"{reg:40s} {c['valu']:6d} {c['salu']:6d} {c['vmem']:5d} {c['lds']:4d} {c['branch']:4d} {c['nop']:6d} {c['waitcnt']:8d} {c['mov']:10d} {c['rebuild']:14d}")
     print("\ntop source lines by static VALU:")
     src = open(SRC).read().split("\n")
     for (f, line), c in sorted(per_line.items(), key=lambda kv: -kv[1]["valu"])[:45]:
