@@ -45,7 +45,7 @@ using pt::fail;
 
 namespace pt {
 int launchCompatWide(int stack, const void* params, hipStream_t st);   // pt_compat.hip
-int compatWideWavesPerCU(int stack, int& n);                            // pt_compat.hip
+int compatWideWavesPerCU(int stack, bool tri, int& n);                  // pt_compat.hip
 }
 
 #define HIP_TRY(expr)                                                                        \
@@ -527,13 +527,28 @@ __device__ __forceinline__ bool deferredRedo(float4 xy, float2 z, float3 o, floa
 // a = s * inv taken times 2^24 -- the same t bit for bit while |s * 2^24 * inv| stays finite,
 // which holds for |inv| <= DevScene::mixLim (a ray with a larger finite |inv| component takes the
 // reference-order query instead: mixUnsafe).
-template <bool MIX = false>
+// DEC3: the scales decoded in three VALU per axis instead of four -- the exponent byte by v_bfe_u32,
+// (byte << 23) + (bias << 23) as one v_lshl_add_u32, the multiply: the same integer into the same
+// multiply.  Only where the register it holds longer is free (the sample-mode TRI render kernels;
+// DESIGN.md section 11 items 15 B and 16): everywhere else it spills or costs a wave per SIMD.
+template <bool MIX = false, bool DEC3 = false>
 __device__ __forceinline__ uint32_t wideHits(uint4 n0, uint4 n1, uint4 n2, uint4 n3, uint4 n4, float3 o, float3 inv,
                                              uint32_t oct, float tmin, float tmax) {
     constexpr uint32_t kMixExp = MIX ? 24u : 0u;   // s * 2^24: the exponent byte + 24 (< 255: mixLim's bound)
-    const float ax = __uint_as_float(((n0.w & 0xffu) + kMixExp) << 23) * inv.x;
-    const float ay = __uint_as_float((((n0.w >> 8) & 0xffu) + kMixExp) << 23) * inv.y;
-    const float az = __uint_as_float((((n0.w >> 16) & 0xffu) + kMixExp) << 23) * inv.z;
+    float ax, ay, az;
+    if constexpr (DEC3) {
+        uint32_t ex, ey, ez;   // (in asm: from `(n0.w >> 8) & 0xff` the compiler makes shift, mask, add, multiply)
+        asm("v_bfe_u32 %0, %1, 0, 8" : "=v"(ex) : "v"(n0.w));
+        asm("v_bfe_u32 %0, %1, 8, 8" : "=v"(ey) : "v"(n0.w));
+        asm("v_bfe_u32 %0, %1, 16, 8" : "=v"(ez) : "v"(n0.w));
+        ax = __uint_as_float((ex << 23) + (kMixExp << 23)) * inv.x;
+        ay = __uint_as_float((ey << 23) + (kMixExp << 23)) * inv.y;
+        az = __uint_as_float((ez << 23) + (kMixExp << 23)) * inv.z;
+    } else {
+        ax = __uint_as_float(((n0.w & 0xffu) + kMixExp) << 23) * inv.x;
+        ay = __uint_as_float((((n0.w >> 8) & 0xffu) + kMixExp) << 23) * inv.y;
+        az = __uint_as_float((((n0.w >> 16) & 0xffu) + kMixExp) << 23) * inv.z;
+    }
     const float bx = (__uint_as_float(n0.x) - o.x) * inv.x;
     const float by = (__uint_as_float(n0.y) - o.y) * inv.y;
     const float bz = (__uint_as_float(n0.z) - o.z) * inv.z;
@@ -1167,6 +1182,9 @@ struct RenderParams {
     // Instanced scenes built with PT_BVH_LIGHTS: lightSlot is indexed by shading index and holds the
     // object's rank among its mesh's sampled lights; instLightFirst: the first record of each instance.
     const uint32_t* instLightFirst;
+    // Flat wide launches: the kernels' TRI instantiations (a triangle-only scene whose edge-form
+    // records S.wprims holds, and PT_WIDE_TRI not 0).  Read by the launchers, not by the kernels.
+    int tri;
 };
 template <bool LIT>
 __device__ __forceinline__ float3 skyOf(const RenderParams& P, float3 d, float3 att) {
@@ -1529,13 +1547,19 @@ __device__ __forceinline__ float3 skyK(float3 d, float3 att) {
 // NEE with INST (scenes built with PT_BVH_LIGHTS): the light records are world-space, one per (instance,
 // emissive triangle); a SHADE step finds its lane back in the world (the marker was popped), so the
 // shadow ray and the parked scatter ray start there like any bounce.
-template <int STACK, bool SAMPLE, bool WIDE, bool INST = false, bool LIT = false, bool NEE = false, bool MIS = false>
+// TRI (with WIDE, not INST): the scene holds no sphere and never did (DevScene::hasSpheres == 0), known
+// when the launch is enqueued (RenderParams::tri): the tests of that flag are compile-time here, and
+// the sphere paths (wideTest<true>, the sphere counters, the window form of bestLo) are not compiled
+// into the step loop.  TRI = false is the kernel for every scene, the flag read at run time.
+template <int STACK, bool SAMPLE, bool WIDE, bool INST = false, bool LIT = false, bool NEE = false, bool MIS = false,
+          bool TRI = false>
 // (NEE on the deeper wide stacks, 16 and 24 entries: 4 waves per SIMD instead of 5 -- at 96 VGPRs the
 // SHADE step's light sample spilled 1-3 registers, and the 24-entry stack's 6 KB of LDS with the
 // 2.5 KB of NEE state fit 4 waves anyway)
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPerEU<STACK, SAMPLE, WIDE> - (NEE && STACK >= 16 ? 1 : 0)))) void renderKernelWF(RenderParams P) {
     static_assert(!NEE || (WIDE && LIT), "NEE: the wide kernels' LIT instantiations only");
     static_assert(!MIS || NEE, "MIS: the NEE instantiations only");
+    static_assert(!TRI || (WIDE && !INST), "TRI: the flat wide kernels only");
     // Deep trees (binary kernels) keep 32 stack entries per lane in LDS (8 KB per wave: 5 waves
     // per SIMD) and the rare deeper entries in global memory (stackSpill, per wave slot and lane).
     constexpr int LS = kLdsStack<STACK, SAMPLE, WIDE>;
@@ -1689,7 +1713,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             /* (t2 counts the start value of a finite interval as a candidate: deferredRedo then  \
                sends a final hit whose box entry lies beyond it to the reference-order query,    \
                which is what wideTest's `closest < b.lo` does for the ray-query kernels) */       \
-            bestLo = INST || kargs()->S.hasSpheres ? -__builtin_inff() : closest;                  \
+            if constexpr (TRI) bestLo = closest;                                                  \
+            else bestLo = INST || kargs()->S.hasSpheres ? -__builtin_inff() : closest;            \
             ng = S.nprims > 0 ? (1u << oc_) : 0u;                                                 \
             /* only camera rays can start far from the scene (a bounce starts on a primitive), and  \
                they all start at the camera: one uniform flag, set on the host (wideFar) */     \
@@ -1724,7 +1749,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #define PT_CRIT_TRACE()                                                                             \
     do {                                                                                          \
         const bool lb_ = S.nprims > 1;                                                            \
-        const bool sph_ = kargs()->S.hasSpheres != 0;                                             \
+        bool sph_ = false;                                                                        \
+        if constexpr (!TRI) sph_ = kargs()->S.hasSpheres != 0;                                    \
         bool redo_ = false;                                                                       \
         for (;;) {                                                                                \
             while (tg) {                                                                          \
@@ -1732,12 +1758,17 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 tg &= tg - 1u;                                                                    \
                 const float4* w_ = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(S.wprims) + mul48(k_)); \
                 const Prim q_{w_[0], w_[1], w_[2]};                                               \
+                if constexpr (TRI) {   /* (no record is a sphere) */                              \
+                    sTris += (uint32_t)__popcll(__ballot(true));                                  \
+                    wideTestTri(q_, __ballot(true), o, d, 0.001f, closest, best, bestLo);         \
+                } else {                                                                          \
                 const bool isS_ = __float_as_uint(q_.p2.w) != 0u;                                 \
                 sTris += (uint32_t)__popcll(__ballot(!isS_));                                     \
                 sSph += (uint32_t)__popcll(__ballot(isS_));                                       \
                 if (sph_) wideTest<true>(q_, o, d, inv, 0.001f, closest, best, bestLo, lb_, redo_, 0u); \
                 else if (INST) wideTest<false>(q_, o, d, inv, 0.001f, closest, best, bestLo, lb_, redo_, 0u); \
                 else wideTestTri(q_, __ballot(true), o, d, 0.001f, closest, best, bestLo);   /* (SHADE decides) */ \
+                }                                                                                 \
             }                                                                                     \
             if ((ng & 0xffu) == 0u) {                                                             \
                 if (sp == 0) break;                                                               \
@@ -2037,7 +2068,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                     const uint4 n2 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 32u, 0, 0));
                     const uint4 n3 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 48u, 0, 0));
                     const uint4 n4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off + 64u, 0, 0));
-                    const uint32_t hits = wideHits<PT_WIDE_MIX != 0>(n0, n1, n2, n3, n4, o, inv, oct & 7u, 0.001f, closest);
+                    const uint32_t hits = wideHits<PT_WIDE_MIX != 0, TRI && SAMPLE>(n0, n1, n2, n3, n4, o, inv, oct & 7u, 0.001f, closest);
                     ng = (n1.x << 8) | (hits >> 24);
                     tgBase = n1.y;
                     tg = hits & 0xffffffu;
@@ -2152,7 +2183,11 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 // (instanced: no reference leaf-box rule; the hit key carries the instance)
                 const bool lb = !INST && S.nprims > 1;
                 const uint32_t kh = INST ? (oct >> 8) << kargs()->S.gBits : 0u;
-                if (kargs()->S.hasSpheres) {   // (uniform: read where needed)
+                if constexpr (TRI) {   // (the triangle-only branch below, alone)
+                    wideTestTri(q0, mL, o, d, 0.001f, closest, best, bestLo);
+                    wideTestTri(q1, m1, o, d, 0.001f, closest, best, bestLo);
+                    sTris += (uint32_t)nL + (uint32_t)__popcll(m1);
+                } else if (kargs()->S.hasSpheres) {   // (uniform: read where needed)
                     if (h0) wideTest<true>(q0, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
                     if (h1) wideTest<true>(q1, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
                     const uint64_t s0 = mL & __ballot(__float_as_uint(q0.p2.w) != 0u);
@@ -2235,7 +2270,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #endif
                 // Triangle-only scenes: the reference's leaf-box rule, decided here for the final
                 // hit alone (deferredRedo; bestLo holds t2)
-                if (!kargs()->S.hasSpheres && S.nprims > 1) {
+                bool triScene = TRI;
+                if constexpr (!TRI) triScene = !kargs()->S.hasSpheres;
+                if (triScene && S.nprims > 1) {
                     if (shading && best >= 0 && !redo) {
                         const float4* bx = kargs()->S.wbox + 2 * (size_t)best;
                         redo = deferredRedo(bx[0], *reinterpret_cast<const float2*>(bx + 1), o, inv, closest, bestLo);
@@ -2449,16 +2486,21 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 // kernels up but slows the compat kernel -- one sequential chain of samples per pixel -- by 3.5 %
 // (DESIGN.md section 6), and it is a per-file option.
 namespace pt {
+// TRI = P.tri: the triangle-only instantiations (critical-pixel waves included)
+template <int S, bool TRI>
+static void launchCompatWideTri(const RenderParams& P, hipStream_t st) {
+    const int grid = P.compatGrid;
+    if (P.nLights > 0 && P.mis) renderKernelWF<S, false, true, false, true, true, true, TRI><<<grid, kWave, 0, st>>>(P);
+    else if (P.nLights > 0) renderKernelWF<S, false, true, false, true, true, false, TRI><<<grid, kWave, 0, st>>>(P);
+    else if (P.lit) renderKernelWF<S, false, true, false, true, false, false, TRI><<<grid, kWave, 0, st>>>(P);
+    else renderKernelWF<S, false, true, false, false, false, false, TRI><<<grid, kWave, 0, st>>>(P);
+}
 int launchCompatWide(int stack, const void* params, hipStream_t st) {
     const RenderParams& P = *static_cast<const RenderParams*>(params);
-    const int grid = P.compatGrid;
     switch (stack) {
 #define PT_COMPAT_WIDE(S)                                                                    \
         case S:                                                                                  \
-            if (P.nLights > 0 && P.mis) renderKernelWF<S, false, true, false, true, true, true><<<grid, kWave, 0, st>>>(P); \
-            else if (P.nLights > 0) renderKernelWF<S, false, true, false, true, true><<<grid, kWave, 0, st>>>(P); \
-            else if (P.lit) renderKernelWF<S, false, true, false, true><<<grid, kWave, 0, st>>>(P); \
-            else renderKernelWF<S, false, true><<<grid, kWave, 0, st>>>(P);                      \
+            P.tri ? launchCompatWideTri<S, true>(P, st) : launchCompatWideTri<S, false>(P, st);   \
             break;
         PT_COMPAT_WIDE(8)
         PT_COMPAT_WIDE(16)
@@ -2468,10 +2510,14 @@ int launchCompatWide(int stack, const void* params, hipStream_t st) {
     }
     return 0;
 }
-int compatWideWavesPerCU(int stack, int& n) {
-    const void* k = stack == 8 ? reinterpret_cast<const void*>(&renderKernelWF<8, false, true>)
-                  : stack == 16 ? reinterpret_cast<const void*>(&renderKernelWF<16, false, true>)
-                  : stack == 24 ? reinterpret_cast<const void*>(&renderKernelWF<24, false, true>) : nullptr;
+template <bool TRI>
+static const void* compatWideKernel(int stack) {
+    return stack == 8 ? reinterpret_cast<const void*>(&renderKernelWF<8, false, true, false, false, false, false, TRI>)
+         : stack == 16 ? reinterpret_cast<const void*>(&renderKernelWF<16, false, true, false, false, false, false, TRI>)
+         : stack == 24 ? reinterpret_cast<const void*>(&renderKernelWF<24, false, true, false, false, false, false, TRI>) : nullptr;
+}
+int compatWideWavesPerCU(int stack, bool tri, int& n) {
+    const void* k = tri ? compatWideKernel<true>(stack) : compatWideKernel<false>(stack);
     if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, kWave, 0) != hipSuccess) return -1;
     return 0;
 }
@@ -3986,6 +4032,18 @@ int setDevice(int dev) {
     return PT_OK;
 }
 
+// Sample mode on a flat scene.  TRI = P.tri: the triangle-only instantiations.
+template <int S, bool LIT, bool TRI>
+void launchSampleWideFlat(const RenderParams& P, hipStream_t st) {
+    if constexpr (LIT) {   // (NEE launches are LIT: a sampled light is an emissive material)
+        if (P.nLights > 0) {
+            if (P.mis) renderKernelWF<S, true, true, false, true, true, true, TRI><<<P.nwaves, kWave, 0, st>>>(P);
+            else renderKernelWF<S, true, true, false, true, true, false, TRI><<<P.nwaves, kWave, 0, st>>>(P);
+            return;
+        }
+    }
+    renderKernelWF<S, true, true, false, LIT, false, false, TRI><<<P.nwaves, kWave, 0, st>>>(P);
+}
 // LIT = P.lit (dispatchRender): the kernels with the emissive exit and the scene's own sky
 template <int S, bool LIT>
 void launchRenderWide(const RenderParams& P, hipStream_t st) {
@@ -4004,16 +4062,9 @@ void launchRenderWide(const RenderParams& P, hipStream_t st) {
         return;
     }
     if (P.pixAcc) {
-        if constexpr (LIT) {   // (NEE launches are LIT: a sampled light is an emissive material)
-            if (P.nLights > 0) {
-                if (P.mis) renderKernelWF<S, true, true, false, true, true, true><<<P.nwaves, kWave, 0, st>>>(P);
-                else renderKernelWF<S, true, true, false, true, true><<<P.nwaves, kWave, 0, st>>>(P);
-                return;
-            }
-        }
-        renderKernelWF<S, true, true, false, LIT><<<P.nwaves, kWave, 0, st>>>(P);
+        P.tri ? launchSampleWideFlat<S, LIT, true>(P, st) : launchSampleWideFlat<S, LIT, false>(P, st);
     } else {
-        pt::launchCompatWide(S, &P, st);   // (its own translation unit, pt_compat.hip; reads P.lit, P.nLights)
+        pt::launchCompatWide(S, &P, st);   // (its own translation unit, pt_compat.hip; reads P.lit, P.nLights, P.tri)
     }
 }
 template <int S, bool LIT>
@@ -4029,10 +4080,10 @@ void launchRender(const RenderParams& P, hipStream_t st) {
     else if (P.pixAcc) renderKernel<S, true, LIT><<<P.ntiles, kWave, 0, st>>>(P);
     else renderKernel<S, false, LIT><<<P.ntiles, kWave, 0, st>>>(P);
 }
-template <int S, bool WIDE, bool INST = false, bool SAMPLE = true>
+template <int S, bool WIDE, bool INST = false, bool SAMPLE = true, bool TRI = false>
 int wavesPerCU(int& n) {
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&renderKernelWF<S, SAMPLE, WIDE, INST>),
-                                                         kWave, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &n, reinterpret_cast<const void*>(&renderKernelWF<S, SAMPLE, WIDE, INST, false, false, false, TRI>), kWave, 0));
     return PT_OK;
 }
 // A run-time stack size as a compile-time constant: f(std::integral_constant<int, N>) for the N
@@ -4051,8 +4102,8 @@ bool withBinStack(int stack, F f) { return withStack<16, 24, 32, 48, 64, 80>(sta
 // waves that fit; compat launches do not ask).  Asked of the kernel without LIT: its LIT twin has
 // the same LDS and waves-per-SIMD attribute, so the same occupancy (DESIGN.md's resource table).
 // The compat wide kernels live in pt_compat.hip's
-// translation unit.
-int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, bool nee, bool mis) {
+// translation unit.  tri: the launch runs a TRI instantiation (RenderParams::tri), which is asked.
+int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, bool nee, bool mis, bool tri) {
     const bool wide = kernel == PT_KERNEL_WIDE;
     if (wide && sample && nee) {   // the NEE and MIS kernels hold more LDS per wave: asked of themselves
         int rc = PT_OK;
@@ -4060,6 +4111,8 @@ int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, 
             constexpr int K = decltype(N)::value;
             const void* k = inst ? (mis ? reinterpret_cast<const void*>(&renderKernelWF<K, true, true, true, true, true, true>)
                                         : reinterpret_cast<const void*>(&renderKernelWF<K, true, true, true, true, true>))
+                          : tri  ? (mis ? reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true, true, true>)
+                                        : reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true, false, true>))
                                  : (mis ? reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true, true>)
                                         : reinterpret_cast<const void*>(&renderKernelWF<K, true, true, false, true, true>));
             const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, kWave, 0);
@@ -4069,11 +4122,11 @@ int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, 
         return rc;
     }
     if (wide && !inst && !sample)
-        return pt::compatWideWavesPerCU(stack, n) ? fail(PT_ERR_STATE, "unsupported wide BVH depth") : PT_OK;
+        return pt::compatWideWavesPerCU(stack, tri, n) ? fail(PT_ERR_STATE, "unsupported wide BVH depth") : PT_OK;
     int rc = PT_OK;
     const bool ok = wide ? withWideStack(stack, [&](auto N) {
         constexpr int K = decltype(N)::value;
-        rc = !inst ? wavesPerCU<K, true>(n) : sample ? wavesPerCU<K, true, true>(n) : wavesPerCU<K, true, true, false>(n);
+        rc = !inst ? (tri ? wavesPerCU<K, true, false, true, true>(n) : wavesPerCU<K, true>(n)) : sample ? wavesPerCU<K, true, true>(n) : wavesPerCU<K, true, true, false>(n);
     }) : withBinStack(stack, [&](auto N) {
         constexpr int K = decltype(N)::value;
         rc = sample ? wavesPerCU<K, false>(n) : wavesPerCU<K, false, false, false>(n);
@@ -4951,7 +5004,11 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     P.S = devScene(s);
     P.S.err = reinterpret_cast<unsigned int*>(f->counters.as<unsigned long long>() + 7);
     // (the render kernels' triangle-only LEAF path reads edge-form records: DevScene::wprims)
-    if (s->wideReady && s->haveWtris && !s->hasSpheres && !s->instanced) P.S.wprims = s->wtris.as<float4>();
+    // The kernels' TRI instantiations read nothing else, so they launch under this one condition
+    // (PT_WIDE_TRI=0: the generic kernels on the same records, for tests and same-library A/B runs).
+    const bool triRecords = s->wideReady && s->haveWtris && !s->hasSpheres && !s->instanced;
+    if (triRecords) P.S.wprims = s->wtris.as<float4>();
+    P.tri = triRecords && kernel == PT_KERNEL_WIDE && envCount("PT_WIDE_TRI", 1) != 0 ? 1 : 0;
     P.cam.pos = make_float3(cam->origin[0], cam->origin[1], cam->origin[2]);
     P.cam.ll = make_float3(cam->lower_left[0], cam->lower_left[1], cam->lower_left[2]);
     P.cam.hor = make_float3(cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]);
@@ -5065,16 +5122,16 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     // occupancy per CU, which the LDS stack caps on deep trees.  Queried once per (device, kernel
     // instantiation) and process.
     auto perCUFor = [&](int& perCU) -> int {
-        static std::atomic<int> cached[16][2][2][2][3][3];   // [device][sample][instanced][wide][stack 8, 16, 24][blind, nee, mis]
+        static std::atomic<int> cached[16][2][2][2][3][3][2];   // [device][sample][instanced][wide][stack 8, 16, 24][blind, nee, mis][tri]
         const bool small = stack <= 24 && stack % 8 == 0 && f->device >= 0 && f->device < 16;
         std::atomic<int>* c = small ? &cached[f->device][sample ? 1 : 0][s->instanced ? 1 : 0]
-                                             [kernel == PT_KERNEL_WIDE ? 1 : 0][stack / 8 - 1][mis ? 2 : nee ? 1 : 0] : nullptr;
+                                             [kernel == PT_KERNEL_WIDE ? 1 : 0][stack / 8 - 1][mis ? 2 : nee ? 1 : 0][P.tri] : nullptr;
         const int known = c ? c->load(std::memory_order_relaxed) : 0;
         if (known > 0) {
             perCU = known;
             return PT_OK;
         }
-        if (int r = persistentWavesPerCU(stack, kernel, perCU, s->instanced, sample, nee, mis)) return r;
+        if (int r = persistentWavesPerCU(stack, kernel, perCU, s->instanced, sample, nee, mis, P.tri != 0)) return r;
         if (c) c->store(perCU, std::memory_order_relaxed);
         return PT_OK;
     };

@@ -38,7 +38,13 @@ def main(tag):
         g.writelines(l for l in lines[1:] if "render" in l or "resolve" in l)
     for p in ("fetch", "write", "tcc", "sq", "valu"):
         if os.path.exists(os.path.join(src, f"pmc_{p}", "run_counter_collection.csv")):
-            shutil.copy(os.path.join(src, f"pmc_{p}", "run_counter_collection.csv"), os.path.join(dst, f"pmc_{p}.csv"))
+            # (the render and resolve kernels' rows: a --full run also dispatches the dynamic scene's
+            # device build, thousands of small launches that would make these files megabytes)
+            with open(os.path.join(src, f"pmc_{p}", "run_counter_collection.csv")) as f, \
+                    open(os.path.join(dst, f"pmc_{p}.csv"), "w") as g:
+                lines = f.readlines()
+                g.write(lines[0])
+                g.writelines(l for l in lines[1:] if "render" in l or "resolve" in l)
 
     bench = json.loads(open(os.path.join(src, "bench.json")).read())
     fetch = render_launches(os.path.join(dst, "pmc_fetch.csv"), "FETCH_SIZE")

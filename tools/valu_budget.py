@@ -95,7 +95,8 @@ def source_regions():
 
 def main() -> None:
     asm = sys.argv[1] if len(sys.argv) > 1 else "/tmp/isa/pt_device_g.s"
-    want = sys.argv[2] if len(sys.argv) > 2 else "renderKernelWFILi8ELb1ELb1ELb0ELb0ELb0ELb0E"
+    # (default: the flagship's triangle-only instantiation; ...ELb0ELb0ELb0ELb0ELb0EE is the generic one)
+    want = sys.argv[2] if len(sys.argv) > 2 else "renderKernelWFILi8ELb1ELb1ELb0ELb0ELb0ELb0ELb1EE"
     text = open(asm).read().split("\n")
     files = {}
     start = None
