@@ -380,6 +380,28 @@ int pt_scene_bvh_info(pt_scene* scene, int* depth, int64_t* n_nodes, int64_t* de
 int pt_scene_wide_info(pt_scene* scene, int* depth, int64_t* node_slots, double* build_ms, int* source);
 /* Download the LBVH in the reference's node layout (2n-1 nodes). */
 int pt_scene_download_bvh(pt_scene* scene, pt_bvh_node* nodes);
+/* Download one array of the current wide tree (the one pt_scene_wide_info describes), byte for byte as
+ * the wide kernels read it.  The layouts are the ones host/pt_wide8.cpp documents and pt_wide8.hpp
+ * sizes (node slots of kW8NodeDwords dwords, 12-dword primitive records, 8-float box records, the
+ * instance rows of pt_instancing.hpp); n = the scene's objects:
+ *   PT_WIDE_NODES       the node slots pt_scene_wide_info reports, from the root (slot 0) on
+ *   PT_WIDE_PRIMS       n x 12 dwords, the primitive records in the tree's leaf order {v0, rank}{v1, .}{v2, .}
+ *                       (an instanced scene: every mesh's records, mesh after mesh)
+ *   PT_WIDE_SHADE       n x 12 dwords, the shading records by reference rank (instanced: by shading index)
+ *   PT_WIDE_BOXES       n x 8 floats, the exact triangle boxes by reference rank (flat scenes)
+ *   PT_WIDE_RANKS       n dwords, LBVH leaf k -> its reference rank (flat scenes)
+ *   PT_WIDE_EDGE_PRIMS  n x 12 dwords, PT_WIDE_PRIMS in edge form {v0, .}{v1 - v0, .}{v2 - v0, .}: only a
+ *                       flat scene that never held a sphere has it
+ *   PT_WIDE_INSTANCES   16 floats per instance {world-to-object rows, objBase, class}: instanced scenes
+ * *bytes (when not NULL) is always set to the array's size, 0 on an error.  out == NULL asks for the
+ * size only; otherwise `capacity` bytes may be written: a capacity below the size is PT_ERR_INVALID
+ * and nothing is written.  An array this scene does not have has 0 bytes and is PT_OK.  PT_ERR_INVALID
+ * for a NULL scene, an unknown array or a negative capacity; PT_ERR_STATE before a build or on a
+ * scene made stale by an update.  Like a query with PT_KERNEL_WIDE, the call builds the wide tree
+ * when the current build has none yet.  It launches nothing: it waits for the device and copies. */
+enum { PT_WIDE_NODES = 0, PT_WIDE_PRIMS = 1, PT_WIDE_SHADE = 2, PT_WIDE_BOXES = 3,
+       PT_WIDE_RANKS = 4, PT_WIDE_EDGE_PRIMS = 5, PT_WIDE_INSTANCES = 6 };
+int pt_scene_download_wide(pt_scene* scene, int array, void* out, int64_t capacity, int64_t* bytes);
 /* RenderManager::hitBvh (render_manager.h:86-135) over a batch of rays, t in [tmin, tmax).
  * rays/hits are host pointers.
  *

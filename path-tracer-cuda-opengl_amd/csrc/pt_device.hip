@@ -3647,6 +3647,7 @@ struct pt_scene {
     std::vector<int64_t> meshFirst, meshCount;
     std::vector<pt_instance> inst;
     DevBuf winst;                           // per instance: world-to-object rows, {objBase, identity}
+    size_t instPrimBytes = 0, instShadeBytes = 0, instWinstBytes = 0;   // wprims, wshade, winst of the full build (pt_scene_download_wide)
     int gBits = 0;                          // hit key = instance << gBits | shading index
     // Instance updates (pt_scene_update_instances).  A full build of a dynamic scene lays the node
     // array out for them -- the top level's region reserved at its upper bound, the mesh trees
@@ -3894,6 +3895,9 @@ int buildInstanced(pt_scene* s, bool lights, hipStream_t st) {
     s->gBits = t.gBits;
     s->wideDepth = t.depth;
     s->wideNodes = (int64_t)(t.nodes.size() / pt::kW8NodeDwords);
+    s->instPrimBytes = t.prims.size() * 4;
+    s->instShadeBytes = t.shade.size() * 4;
+    s->instWinstBytes = t.winst.size() * 4;
     s->wideSource = 3;
     s->wideReady = true;
     s->deviceBytes = bytes;
@@ -4720,6 +4724,38 @@ int pt_scene_download_bvh(pt_scene* s, pt_bvh_node* out) {
     if (L == 0) {   // single object: the root is the leaf (bvh.h:76-81 with numObjects = 1)
         for (int a = 0; a < 3; a++) { out[0].bmin[a] = leafBoxes[a]; out[0].bmax[a] = leafBoxes[3 + a]; }
     }
+    return PT_OK;
+}
+
+int pt_scene_download_wide(pt_scene* s, int array, void* out, int64_t capacity, int64_t* bytes) {
+    if (bytes) *bytes = 0;
+    if (!s) return fail(PT_ERR_INVALID, "pt_scene_download_wide: null scene");
+    if (array < PT_WIDE_NODES || array > PT_WIDE_INSTANCES) return fail(PT_ERR_INVALID, "pt_scene_download_wide: unknown array");
+    if (capacity < 0) return fail(PT_ERR_INVALID, "pt_scene_download_wide: negative capacity");
+    if (!s->built) return fail(PT_ERR_STATE, "pt_scene_download_wide: BVH not built");
+    int rc = setDevice(s->device);
+    if (rc) return rc;
+    if ((rc = ensureWide(s))) return rc;   // (first use: builds the tree, as a query does)
+    // the arrays as the kernels read them (devScene): a flat scene's are sized by its objects, an
+    // instanced scene's by its full build
+    const size_t n = s->wideReady && !s->instanced ? (size_t)s->nobj : 0;
+    const DevBuf* src = nullptr;
+    size_t size = 0;
+    switch (array) {
+    case PT_WIDE_NODES: src = &s->wide; size = s->wideReady ? (size_t)s->wideNodes * pt::kW8NodeDwords * 4 : 0; break;
+    case PT_WIDE_PRIMS: src = &s->wprims; size = s->instanced ? s->instPrimBytes : n * pt::kW8PrimDwords * 4; break;
+    case PT_WIDE_SHADE: src = &s->wshade; size = s->instanced ? s->instShadeBytes : n * 48; break;
+    case PT_WIDE_BOXES: src = &s->wbox; size = n * pt::kW8BoxFloats * 4; break;
+    case PT_WIDE_RANKS: src = &s->rankOf; size = n * 4; break;
+    case PT_WIDE_EDGE_PRIMS: src = &s->wtris; size = s->haveWtris ? n * pt::kW8PrimDwords * 4 : 0; break;
+    default: src = &s->winst; size = s->instanced ? s->instWinstBytes : 0; break;
+    }
+    if (size > 0 && (!src->p || src->cap < size)) return fail(PT_ERR_STATE, "pt_scene_download_wide: the array is smaller than the tree reports");
+    if (bytes) *bytes = (int64_t)size;
+    if (!out || size == 0) return PT_OK;
+    if ((uint64_t)capacity < size) return fail(PT_ERR_INVALID, "pt_scene_download_wide: capacity below the array's size");
+    HIP_TRY(hipDeviceSynchronize());   // (a build has finished when it returns; renders only read the arrays)
+    HIP_TRY(hipMemcpy(out, src->p, size, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -65,6 +65,12 @@ OUT_RGB32F, OUT_RGBA8, OUT_RGBA8_SURFACE = 0, 1, 2
 
 
 KERNEL_DEFAULT, KERNEL_SIMPLE, KERNEL_WAVEFRONT, KERNEL_WIDE = 0, 1, 2, 3
+# pt_scene_download_wide's arrays (Scene.download_wide) and the shape of one record of each
+WIDE_NODES, WIDE_PRIMS, WIDE_SHADE, WIDE_BOXES, WIDE_RANKS, WIDE_EDGE_PRIMS, WIDE_INSTANCES = range(7)
+WIDE_NODE_DWORDS = 20
+_WIDE_RECORD = {WIDE_NODES: (np.uint32, WIDE_NODE_DWORDS), WIDE_PRIMS: (np.uint32, 12), WIDE_SHADE: (np.uint32, 12),
+                WIDE_BOXES: (np.float32, 8), WIDE_RANKS: (np.uint32, 0), WIDE_EDGE_PRIMS: (np.uint32, 12),
+                WIDE_INSTANCES: (np.float32, 16)}
 
 
 class SceneDesc(C.Structure):
@@ -96,7 +102,7 @@ EXPORTS = [
     "pt_scene_build_bvh_ex", "pt_film_stats", "pt_preset_instanced", "pt_instanced_desc_free",
     "pt_scene_create_instanced", "pt_trace_occluded", "pt_trace_occluded_device",
     "pt_scene_update_instances", "pt_scene_set_sky", "pt_preset_sky", "pt_scene_light_count",
-    "pt_scene_download_lights",
+    "pt_scene_download_lights", "pt_scene_download_wide",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -142,6 +148,7 @@ _sig = {
     "pt_scene_update_instances": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
     "pt_scene_bvh_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pt_scene_download_bvh": (C.c_int, [_P, _P]),
+    "pt_scene_download_wide": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "pt_scene_wide_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                      C.POINTER(C.c_int)]),
     "pt_trace_closest": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_float, _P, C.POINTER(Stats)]),
@@ -426,6 +433,19 @@ class Scene:
         out = np.zeros(max(0, 2 * n - 1), NODE_DTYPE)
         _check(lib.pt_scene_download_bvh(self.h, _ptr(out) if len(out) else None), "pt_scene_download_bvh")
         return out
+
+    def download_wide(self, array: int) -> np.ndarray:
+        """pt_scene_download_wide: one array of the current wide tree as the kernels read it (built at
+        first use, like a wide query): WIDE_NODES (slots, 20) uint32, WIDE_PRIMS / WIDE_SHADE /
+        WIDE_EDGE_PRIMS (n, 12) uint32, WIDE_BOXES (n, 8) float32, WIDE_RANKS (n,) uint32, WIDE_INSTANCES
+        (instances, 16) float32; an array the scene does not have is empty."""
+        size = C.c_int64()
+        _check(lib.pt_scene_download_wide(self.h, array, None, 0, C.byref(size)), "pt_scene_download_wide")
+        dtype, width = _WIDE_RECORD[array]
+        out = np.zeros(size.value // 4, dtype)
+        if size.value:
+            _check(lib.pt_scene_download_wide(self.h, array, _ptr(out), out.nbytes, C.byref(size)), "pt_scene_download_wide")
+        return out.reshape(-1, width) if width else out
 
     def trace(self, rays: np.ndarray, tmin: float = 0.001, tmax: float = float("inf"), kernel: int = KERNEL_DEFAULT):
         """Closest hits (pt_trace_closest_ex): kernel=KERNEL_WIDE traverses the 8-wide tree."""

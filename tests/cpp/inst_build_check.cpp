@@ -6,6 +6,19 @@
 // planes, as nodeChildren does) around the fp64 world image of what lies below them, the layout
 // and the scalars.  A failed build prints "rc <code>: <message>" and exits 3.
 // usage: inst_build_check objects.bin meshes.bin instances.bin materials.bin dynamic rebraid budget
+//
+// With five more arguments it checks arrays downloaded from a scene on the device
+// (pt_scene_download_wide: PT_WIDE_NODES and PT_WIDE_INSTANCES, pt_scene_wide_info's depth and
+// slots) in place of the ones it built (tests/test_gpu_wide_structure.py; the package Makefile
+// builds tools/micro/inst_build_check for it).  It still runs the host build on the scene files,
+// which gives the layout (topCap, meshRoot, the entries) and the rows expected for these matrices:
+//   ... nodes.bin winst.bin depth slots full   the arrays of a full build (source 3): byte for byte the host's
+//   ... nodes.bin winst.bin depth slots top    after pt_scene_update_instances and a rebuild of the top
+//       level on the device (source 4; instances.bin holds the new matrices): the rows are the host's,
+//       and the walk above runs on the downloaded nodes, whose mesh trees are the first build's.
+// In both the reported depth must be the walk's (top levels + the marker + the deepest mesh tree + 1)
+// and the reported slots the layout's.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -58,6 +71,8 @@ struct Walk {
     uint32_t maxTop = 0;
     size_t entries = 0;       // instance records reached
     int64_t steps = 0;
+    double margin = 0.0;      // what an entry's planes keep around the world image below it
+    int topDepth = 0;         // deepest node of the top level (root = 1; instance records not counted)
 
     const uint32_t* node(uint32_t s) const { return &t.nodes[(size_t)s * pt::kW8NodeDwords]; }
 
@@ -110,7 +125,7 @@ struct Walk {
             auto inside = [&](double x, double y, double z) {
                 for (int a = 0; a < 3; a++) {
                     const double w = (double)I.m[4 * a] * x + (double)I.m[4 * a + 1] * y + (double)I.m[4 * a + 2] * z + (double)I.m[4 * a + 3];
-                    if (!(lo[a] <= w && w <= hi[a])) return false;
+                    if (!(lo[a] <= w - margin && w + margin <= hi[a])) return false;
                 }
                 return true;
             };
@@ -127,8 +142,9 @@ struct Walk {
     }
 
     // a node of the top level: every child is internal (a node or an instance record)
-    void top(uint32_t s) {
+    void top(uint32_t s, int level = 1) {
         const uint32_t* R = node(s);
+        topDepth = level > topDepth ? level : topDepth;
         float p[3];
         std::memcpy(p, R, 12);
         for (int j = 0; j < 8; j++) {
@@ -148,7 +164,7 @@ struct Walk {
                 hi[a] = (double)p[a] + std::ldexp((double)qh, e);
             }
             if (node(c)[3] == pt::kW8InstanceFlag) entry(c, lo, hi);
-            else top(c);
+            else top(c, level + 1);
         }
     }
 };
@@ -196,6 +212,30 @@ int main(int argc, char** argv) {
         return 3;
     }
     check(pt::buildInstancedTree(in, again) == PT_OK && sameTree(t, again), "two builds give byte-identical arrays");
+    // downloaded arrays in place of the built ones
+    const std::string mode = argc >= 13 ? argv[12] : "";
+    int repDepth = t.depth;
+    int64_t repSlots = (int64_t)(t.nodes.size() / pt::kW8NodeDwords);
+    if (argc >= 13) {
+        if (mode != "full" && mode != "top") return 2;
+        const std::vector<uint32_t> dn = readAll<uint32_t>(argv[8]);
+        const std::vector<float> dw = readAll<float>(argv[9]);
+        repDepth = std::atoi(argv[10]);
+        repSlots = std::atoll(argv[11]);
+        check(dn.size() == t.nodes.size(), "downloaded node array has the layout's size");
+        check(repSlots == (int64_t)(t.nodes.size() / pt::kW8NodeDwords), "reported slots are the layout's");
+        check(dw.size() == t.winst.size() && std::memcmp(dw.data(), t.winst.data(), dw.size() * 4) == 0,
+              "downloaded instance rows equal the host's rows for these matrices");
+        if (mode == "full")
+            check(dn.size() == t.nodes.size() && std::memcmp(dn.data(), t.nodes.data(), dn.size() * 4) == 0,
+                  "downloaded nodes equal the host build's");
+        if (failures) {
+            std::printf("slots %zu top %u failures %d\n", t.nodes.size() / pt::kW8NodeDwords, t.topCap, failures);
+            return 1;
+        }
+        t.nodes = dn;
+        t.winst = dw;
+    }
 
     const size_t ni = sc.inst.size();
     const uint32_t slots = (uint32_t)(t.nodes.size() / pt::kW8NodeDwords);
@@ -209,8 +249,40 @@ int main(int argc, char** argv) {
     for (int m = 0; m + 1 < nm; m++) check(t.meshRoot[(size_t)m] <= t.meshRoot[(size_t)m + 1], "mesh trees in mesh order");
 
     Walk w{sc, t, slots, std::vector<int>(ni * (size_t)sc.gTotal, 0), std::vector<int>(t.topCap, 0)};
+    // The top level's own margin: 2^emin of its root box (buildWide8Leaf; wideWriteKernel's rule on
+    // the device).  The root box is the union of the entries' boxes, which contain the world image
+    // of the primitives, so the extent taken from that image in fp64 is never larger than the
+    // builder's and this margin never more than the one the builder kept.
+    {
+        double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (size_t i = 0; i < ni; i++) {
+            const pt_instance& I = sc.inst[i];
+            for (int64_t k = 0; k < sc.count[(size_t)I.mesh]; k++) {
+                const pt_object& o = sc.objs[(size_t)(sc.first[(size_t)I.mesh] + k)];
+                auto grow = [&](double x, double y, double z) {
+                    for (int a = 0; a < 3; a++) {
+                        const double v = (double)I.m[4 * a] * x + (double)I.m[4 * a + 1] * y + (double)I.m[4 * a + 2] * z + (double)I.m[4 * a + 3];
+                        mn[a] = std::fmin(mn[a], v);
+                        mx[a] = std::fmax(mx[a], v);
+                    }
+                };
+                if (o.type == PT_SPHERE) {
+                    const double rr = std::fabs((double)o.v[3]);
+                    for (int c = 0; c < 8; c++) grow(o.v[0] + ((c & 1) ? rr : -rr), o.v[1] + ((c & 2) ? rr : -rr), o.v[2] + ((c & 4) ? rr : -rr));
+                } else {
+                    for (int v = 0; v < 3; v++) grow(o.v[3 * v], o.v[3 * v + 1], o.v[3 * v + 2]);
+                }
+            }
+        }
+        double ext = 0.0;
+        for (int a = 0; a < 3; a++) ext = std::fmax(ext, std::fmax(std::fmax(std::fabs(mn[a]), std::fabs(mx[a])), mx[a] - mn[a]));
+        const int emin = ext > 0.0 && std::isfinite(ext) ? std::max(-100, (int)std::ceil(std::log2(ext)) - pt::kW8EminShift) : -100;
+        w.margin = std::ldexp(1.0, emin);
+    }
     check(w.node(0)[3] != pt::kW8InstanceFlag, "slot 0 is a node");
     w.top(0);
+    check(repDepth == w.topDepth + 1 + t.maxDepthB + 1, "reported depth is the walk's: top levels, the marker, the deepest mesh tree");
+    check(pt::wideStackFor(repDepth) >= 0, "wideStackFor(reported depth) >= 0");
     check(w.entries == t.entries.size(), "one instance record per entry");
     for (size_t i = 0; i < ni; i++) {
         const int mesh = sc.inst[i].mesh;

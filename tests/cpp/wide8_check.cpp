@@ -2,10 +2,11 @@
 // kernels run (TEST INFRASTRUCTURE: compiled and run by tests/test_wide_builder.py; the product
 // never uses it).  Reads objects and rays, builds the binary LBVH with the oracle (oracle/), the
 // reference ranks and the wide tree exactly as libpt does, then
-//   1. checks the tree: every primitive once, child boxes contain the exact primitive boxes
+//   1. checks the tree (wide_tree_checks.hpp, the checks every builder's tree passes): every
+//      primitive once and referenced by one leaf, child boxes contain the exact primitive boxes
 //      with at least the tree's smallest quantum 2^emin to spare on every side (the outward margin
 //      the traversal's rounding bound needs, pt_device.hip wideHits), node/primitive encodings in
-//      range;
+//      range, the reported depth and slots those of the walk;
 //   2. traces every ray through a scalar restatement of renderKernelWF<.., WIDE>'s NODE / LEAF
 //      steps (nearest-first slots, conservative quantised slab test, (t, tie rank) minimum,
 //      the reference's leaf box test, the redo rule) and writes {leaf k or -1, t, redo} per ray.
@@ -20,6 +21,7 @@
 
 #include "pt.h"
 #include "pt_wide8.hpp"
+#include "wide_tree_checks.hpp"
 
 extern "C" {
 typedef struct { int32_t left, right, parent, objid; float bmin[3], bmax[3]; } orc_node;
@@ -172,9 +174,6 @@ std::vector<T> readAll(const char* path) {
     return v;
 }
 int failures = 0;
-void check(bool ok, const std::string& what) {
-    if (!ok && failures++ < 10) std::fprintf(stderr, "CHECK FAILED: %s\n", what.c_str());
-}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -210,84 +209,19 @@ int main(int argc, char** argv) {
     }
     P = w.prims.data();
     N = w.nodes.data();
-    // 1. structure.  The smallest quantum, as the builder takes it: 2^-kW8EminShift (pt_wide8.hpp) of the larger of the
-    // scene's extent and coordinates (rounded up to a power of two)
-    double ext = 0.0;
-    {
-        double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int64_t k = 0; k < n; k++)
-            for (int a = 0; a < 3; a++) {
-                mn[a] = std::fmin(mn[a], (double)boxes[(size_t)k * 6 + a]);
-                mx[a] = std::fmax(mx[a], (double)boxes[(size_t)k * 6 + 3 + a]);
-            }
-        for (int a = 0; a < 3; a++) ext = std::fmax(ext, std::fmax(std::fmax(std::fabs(mn[a]), std::fabs(mx[a])), mx[a] - mn[a]));
-    }
-    const int emin = ext > 0.0 ? std::max(-100, (int)std::ceil(std::log2(ext)) - pt::kW8EminShift) : -100;
-    const double minQuantum = std::ldexp(1.0, emin);
-    std::vector<int> seen((size_t)n, 0);
+    // 1. structure: the checks of wide_tree_checks.hpp on the arrays just built (the host build has no
+    // capacity of its own: 2^24 slots is the encoding's)
     std::vector<int> kOfRank((size_t)n, -1);
     for (int64_t k = 0; k < n; k++) kOfRank[rank[k]] = (int)k;
-    for (int64_t i = 0; i < n; i++) {
-        const uint32_t rk = w.prims[(size_t)i * 12 + 3];
-        check(rk < (uint32_t)n, "rank in range");
-        if (rk < (uint32_t)n) seen[rk]++;
-    }
-    for (int64_t k = 0; k < n; k++) check(seen[k] == 1, "every primitive exactly once");
-    const int64_t slots = (int64_t)(w.nodes.size() / 20);
-    int64_t reached = 0;
-    std::vector<int64_t> todo{0};
-    while (!todo.empty()) {
-        const int64_t s = todo.back();
-        todo.pop_back();
-        reached++;
-        const uint32_t* R = &w.nodes[(size_t)s * 20];
-        for (int j = 0; j < 8; j++) {
-            const uint32_t meta = ((j < 4 ? R[6] : R[7]) >> (8 * (j & 3))) & 0xffu;
-            if (!meta) continue;
-            double lo[3], hi[3];   // exact child planes
-            for (int a = 0; a < 3; a++) {
-                const double sc = std::ldexp(1.0, (int)((R[3] >> (8 * a)) & 0xffu) - 127);
-                const uint32_t ql = (R[8 + 4 * a + (j >> 2)] >> (8 * (j & 3))) & 0xffu;
-                const uint32_t qh = (R[10 + 4 * a + (j >> 2)] >> (8 * (j & 3))) & 0xffu;
-                lo[a] = (double)u2f(R[a]) + ql * sc;
-                hi[a] = (double)u2f(R[a]) + qh * sc;
-            }
-            auto contains = [&](int64_t prim) {
-                const int64_t k = kOfRank[w.prims[(size_t)prim * 12 + 3]];
-                for (int a = 0; a < 3; a++)
-                    if (!(lo[a] <= (double)boxes[(size_t)k * 6 + a] - minQuantum &&
-                          hi[a] >= (double)boxes[(size_t)k * 6 + 3 + a] + minQuantum))
-                        return false;
-                return true;
-            };
-            if ((meta & 0x18u) == 0x18u) {
-                const int64_t c = (int64_t)R[4] + (meta & 7u);
-                check(c < slots && (meta & 7u) == (uint32_t)j, "child slot in range");
-                if (c < slots) todo.push_back(c);
-                // every primitive below the child lies strictly inside its planes
-                std::vector<int64_t> sub{c};
-                while (!sub.empty()) {
-                    const int64_t x = sub.back();
-                    sub.pop_back();
-                    const uint32_t* X = &w.nodes[(size_t)x * 20];
-                    for (int jj = 0; jj < 8; jj++) {
-                        const uint32_t m = ((jj < 4 ? X[6] : X[7]) >> (8 * (jj & 3))) & 0xffu;
-                        if (!m) continue;
-                        if ((m & 0x18u) == 0x18u) sub.push_back((int64_t)X[4] + (m & 7u));
-                        else
-                            for (uint32_t q = 0; q < 3 && ((m >> 5) >> q & 1u); q++)
-                                check(contains((int64_t)X[5] + (m & 31u) + q), "subtree primitive inside child box");
-                    }
-                }
-            } else {
-                const uint32_t cnt = (meta >> 5) == 1u ? 1u : ((meta >> 5) == 3u ? 2u : 3u);
-                check((meta >> 5) == 1u || (meta >> 5) == 3u || (meta >> 5) == 7u, "unary leaf count");
-                check((meta & 31u) + cnt <= 24u, "leaf offset < 24");
-                for (uint32_t q = 0; q < cnt; q++) check(contains((int64_t)R[5] + (meta & 31u) + q), "leaf inside box");
-            }
-        }
-    }
-    check(reached == w.usedNodes, "every used node reachable once");
+    const int64_t slots = (int64_t)(w.nodes.size() / pt::kW8NodeDwords);
+    widecheck::Report rep;
+    const widecheck::WideArrays arrays{w.nodes.data(), slots, w.prims.data(), n, prims.data(), boxes.data(), rank.data(),
+                                       w.depth, slots, (int64_t)1 << 24};
+    const widecheck::WalkResult walk = widecheck::checkWideTree(arrays, rep);
+    rep.check(walk.reached == w.usedNodes, "every used node reachable once", walk.reached, w.usedNodes);
+    rep.check(walk.leaves == w.leaves, "leaf children counted", walk.leaves, w.leaves);
+    rep.summary();
+    failures += (int)rep.failures;
     // 2. traversal
     std::vector<float> out((size_t)nr * 3);
     for (int64_t i = 0; i < nr; i++) {
