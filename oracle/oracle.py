@@ -1,7 +1,8 @@
 """ctypes wrapper of oracle/liboracle.so — the CPU restatement (TEST INFRASTRUCTURE ONLY).
 
 Imported only by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg, as the
-checker; the product (libpt.so) never uses it.  Parity status: see pt_oracle.h.
+checker; the product (libpt.so) never uses it.  Parity status: see pt_oracle.h (refharness.py,
+next to this file, runs the reference's own code for the comparison).
 """
 from __future__ import annotations
 
@@ -116,7 +117,8 @@ def curand_uniform(state: np.ndarray, count: int) -> np.ndarray:
 def set_draw_order(zyx: bool) -> None:
     """Test-only: draw vec3(u - 0.5f, u - 0.5f, u - 0.5f)'s three coordinates z, y, x instead of x, y, z.
     utility.h:55-58 / 76-79 leave the order to the compiler (C++ argument evaluation order is
-    unspecified); the oracle's default x, y, z is an assumption (pt_oracle.cpp draw3)."""
+    unspecified): False (x, y, z, the default) is the reference built with the ROCm clang++, True is
+    the reference built with g++; both are pinned bit for bit (tests/test_reference_parity.py)."""
     lib.orc_set_draw_order(1 if zyx else 0)
 
 

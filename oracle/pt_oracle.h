@@ -6,12 +6,15 @@
  * cpu_baseline leg, and by nothing else.  The product (libpt.so) never
  * links, loads or calls it.
  *
- * Parity status: pinned statistically against the reference's committed
- * render output2/exp2.png (TRIANGLEWORLD, see tests/golden/); the LBVH
- * topology, closest-hit and scatter restatements follow the reference
- * source line by line (citations in pt_oracle.cpp).  The reference itself
- * cannot be built here (needs nvcc + cuRAND + GLFW), so
- * bit-level parity against a reference binary is unpinned.
+ * Parity status: pinned bit for bit against the reference's OWN code, compiled for the CPU
+ * (oracle/ref/: the reference's headers and its rayTracing / initRandom / render behind a small
+ * shim, built into oracle/_ref/ by `make ref` with g++ and with the ROCm clang++ wherever a
+ * reference tree is present; tests/test_reference_parity.py, and tests/golden/reference_fixtures.npz
+ * for machines without one): Morton keys, LBVH topology and origin-seeded boxes, closest hits on
+ * ordinary and degenerate rays, Material::scatter, the camera, whole frames and the streams after
+ * them.  Pinned statistically against the reference's committed renders (output2/exp2.png and the
+ * chapter images, see tests/golden/).  What stays unpinned is the CUDA toolchain (nvcc's code
+ * generation, CUDA's powf) and cuRAND itself.
  *
  * All structs are plain C, binary-identical to include/pt.h's.
  */
@@ -47,7 +50,10 @@ void orc_xorwow_init_range(uint64_t seed, uint64_t first, int64_t count, uint32_
 void orc_xorwow_skip_subsequences(uint32_t state[6], uint64_t n);   /* state := state after n*2^67 draws */
 uint32_t orc_xorwow_next(uint32_t state[6]);
 float orc_curand_uniform(uint32_t state[6]);
-/* test-only: 1 = the three draws of vec3(u-0.5f, u-0.5f, u-0.5f) taken z, y, x (an unpinned choice, see draw3) */
+/* test-only: 1 = the three draws of vec3(u-0.5f, u-0.5f, u-0.5f) taken z, y, x.  C++ leaves the order to
+ * the compiler: 0 (x, y, z, the default and the kernels') is what the ROCm clang++ build of the reference
+ * does, 1 is what its g++ build does; both are pinned bit for bit (tests/test_reference_parity.py).  Which
+ * of the two nvcc chose is the one thing no build here can tell (see draw3). */
 void orc_set_draw_order(int zyx);
 
 /* utils/morton_code.h:29-75; include_origin=1 reproduces maxBox starting as the zero box */
