@@ -545,6 +545,67 @@ int pt_render_ex(pt_scene* scene, pt_film* film, const pt_camera* cam, int spp, 
 /* Work counters and kernel time of the film's last pt_render / pt_render_ex; waits for that
  * frame to finish.  Reports PT_ERR_STATE if a traversal guard tripped in it (corrupt tree). */
 int pt_film_stats(pt_film* film, pt_stats* stats);
+/* First-hit guide buffers ("AOVs": albedo, normal, position, depth of what each pixel sees first), the
+ * input of any denoiser.  One pt_aov per pixel of the film's rows, local rows in order, three 16-byte
+ * rows each.  A pixel depends on nothing else, so a partitioned film writes its rows of the full frame.
+ * The pixel's ray is the camera ray through the pixel centre, in the render kernels' operation order
+ * (W, H = the film's full frame; every operation one rounded fp32 operation):
+ *   u = ((float)col + 0.5f) * (1.0f / W);   v = ((float)globalRow + 0.5f) * (1.0f / H)
+ *   o = cam.origin;   d = ((lower_left + u * horizontal) + v * vertical) - origin
+ * No random number is drawn and the lens is ignored (a thin-lens camera's AOVs are those of its lens
+ * centre); the film's streams, accumulators and pt_film_stats are not touched.
+ * The record is defined by the hit record h that pt_trace_closest_ex(scene, ray, tmin = 0.001, tmax =
+ * +inf, PT_KERNEL_WIDE) returns for that ray -- flat and instanced scenes alike (an instanced record is
+ * that query's, far-origin shift included); the 8-wide tree is built at first use, like any wide query.
+ *   hit:  p = h.p, n = h.n (facing the ray), obj = h.obj, mat = h.mat,
+ *         depth = h.t * sqrtf((d.x * d.x + d.y * d.y) + d.z * d.z),
+ *         albedo = the material's albedo for PT_LAMBERTIAN and PT_METAL, fminf(E, 1) per channel for
+ *         PT_EMISSIVE, (1, 1, 1) for PT_DIELECTRIC and any other type
+ *   miss: obj = mat = -1, albedo = (1, 1, 1), n = p = 0, depth = 0
+ * Execution as pt_render: `out` is a device pointer when out_on_device != 0 (16-byte aligned: the rows
+ * are written and, by pt_film_denoise, read as 16-byte words; `stream` is then the hipStream_t to use, may
+ * be NULL), else a host pointer; asynchronous when out_on_device != 0 and stats ==
+ * NULL, otherwise the call returns when the records are written.  stats: rays = the film's pixels, paths
+ * = 0, the node / box / primitive counters and kernel_ms as for a trace (the scene's query counters are
+ * used: like the ray queries, calls on one scene must not overlap).
+ * PT_ERR_INVALID for a NULL argument or a scene and film on different devices; PT_ERR_STATE before a
+ * build or on a stale scene. */
+typedef struct { float albedo[3]; float depth; float n[3]; int32_t obj; float p[3]; int32_t mat; } pt_aov;   /* 48 B */
+int pt_render_aov(pt_scene* scene, pt_film* film, const pt_camera* cam, pt_aov* out, int out_on_device,
+                  void* stream, pt_stats* stats);
+/* An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by the AOVs, for low-spp frames.
+ * rgb and out are W x H x 3 floats in film order, aov W x H records; on_device = 0: host pointers, copied
+ * in and out, the call is synchronous; on_device != 0: device pointers, the passes are enqueued on
+ * `stream` and the call returns without waiting.  out may equal rgb: the passes ping-pong through two
+ * film-owned scratch images, allocated at first use and kept (so calls on one film use one stream, or are
+ * ordered by the caller).  Only a film that owns the whole frame (n_parts == 1): a stripe would need
+ * halos.  The filter is domain-agnostic; callers pass pt_render's output as it is.
+ * opts: NULL means {5, 0.6f, 0.1f, 0.02f}; iterations in [0, 8] (0 is a copy), every sigma finite and
+ * > 0.  PT_ERR_INVALID -- before anything is enqueued, `out` untouched -- for anything else, for a NULL
+ * film, rgb, aov or out, and for a partitioned film.
+ * Pass i = 0 .. iterations - 1, one kernel launch each: s = 1 << i, c = the current image (the input in
+ * pass 0).  Every operation is one rounded fp32 operation in the written order (no contraction, IEEE
+ * division, denormals kept); dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z.
+ *   isa2 = 1.0f / (sigma_albedo * sigma_albedo);   sc_i = sigma_color * 2^-i (exact);
+ *   isc2 = 1.0f / (sc_i * sc_i)
+ * Pixel (x, y) with record P, hitP = P.obj >= 0:  acc = 0, ws = 0; taps dy = -2..2 outer, dx = -2..2
+ * inner, q = (x + dx * s, y + dy * s); a tap outside the frame is skipped.
+ *   h = k[|dx|] * k[|dy|], k = {0.375, 0.25, 0.0625}.  The centre tap has w = h.  Any other tap, with
+ *   record Q: skipped when (Q.obj >= 0) != hitP.
+ *   hitP:  wn = fmaxf(0, dot(P.n, Q.n)), then wn = wn * wn six times;  dp = Q.p - P.p;
+ *          dist = fabsf(dot(P.n, dp));  xx = dist / (sigma_plane * P.depth);  wp = 1 / (1 + xx * xx)
+ *   else:  wn = wp = 1
+ *   da = Q.albedo - P.albedo;  wa = 1 / (1 + dot(da, da) * isa2)
+ *   dc = c[q] - c[p];          wc = 1 / (1 + dot(dc, dc) * isc2)
+ *   w = (((h * wn) * wp) * wa) * wc;   a tap whose w is not > 0 (0 or NaN) is skipped
+ *   a kept tap:  acc.ch = acc.ch + w * c[q].ch per channel,  ws = ws + w
+ * "Skipped" means not added: 0 x inf never appears.  Then out.ch = acc.ch / ws.  The centre tap is always
+ * kept, so ws > 0; a NaN centre stays NaN.
+ * First-hit guides see the reflector, not the reflection: what a mirror or a glass ball shows is
+ * filtered with the guides of the mirror or the ball. */
+typedef struct { int32_t iterations; float sigma_color, sigma_albedo, sigma_plane; int32_t reserved[4]; } pt_denoise_opts;
+int pt_film_denoise(pt_film* film, const float* rgb, const pt_aov* aov, float* out, int on_device, void* stream,
+                    const pt_denoise_opts* opts);
 /* Re-initialise the film's streams to their initRandom state (asynchronous on `stream`). */
 int pt_film_reset(pt_film* film, void* stream);
 /* Progressive rendering: zero the film's accumulated sums (asynchronous on `stream`); the number

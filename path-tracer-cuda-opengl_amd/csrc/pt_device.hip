@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "../host/pt_denoise_dev.hpp"
 #include "../host/pt_error.hpp"
 #include "../host/pt_host.hpp"
 #include "../host/pt_inst_dev.hpp"
@@ -2851,19 +2852,29 @@ __device__ __forceinline__ void wideGroupClosest(const DevScene& S, WideWalk& w,
         else wideTest<false>(q, w.o, w.d, w.inv, w.tminI, b.closest, b.best, b.bestLo, lb, b.redo, kh);
     }
 }
-// The finished walk's record, the same as traceKernel's.
+// The finished walk's hit: false for a miss, else the shading record x and the distance t along the
+// query's ray (what the trace kernels report, what the AOV kernel reads the material from).
 template <bool INST>
-__device__ __forceinline__ pt_hit wideHit(const DevScene& S, const WideWalk& w, WideBest& b, float tmin, float tmax) {
+__device__ __forceinline__ bool wideHitRec(const DevScene& S, const WideWalk& w, WideBest& b, float tmin, float tmax,
+                                           HitRec& x, float& t) {
     if (b.redo) {   // an order-dependent candidate: the query in the reference's order
         b.closest = tmax;
         const int k = traceRefStackless(S, w.o, w.d, tmin, b.closest);
         b.best = k >= 0 ? (int)S.rankOf[k] : -1;
     }
-    if (b.best < 0) return missRecord();
+    if (b.best < 0) return false;
     int obj = 0;
-    const HitRec x = INST ? makeHitInst(S, (uint32_t)b.best & kPrimMask, b.closest, w.wo2, w.wd, obj)
-                          : makeHitFrom(S.wshade, b.best & (int)kPrimMask, b.closest, w.o, w.d);
-    return hitRecord(x, INST ? b.closest + w.shift : b.closest);
+    x = INST ? makeHitInst(S, (uint32_t)b.best & kPrimMask, b.closest, w.wo2, w.wd, obj)
+             : makeHitFrom(S.wshade, b.best & (int)kPrimMask, b.closest, w.o, w.d);
+    t = INST ? b.closest + w.shift : b.closest;
+    return true;
+}
+// The finished walk's record, the same as traceKernel's.
+template <bool INST>
+__device__ __forceinline__ pt_hit wideHit(const DevScene& S, const WideWalk& w, WideBest& b, float tmin, float tmax) {
+    HitRec x;
+    float t;
+    return wideHitRec<INST>(S, w, b, tmin, tmax, x, t) ? hitRecord(x, t) : missRecord();
 }
 
 // pt_trace_closest on the binary LBVH, in the reference order (trace<STACK>).
@@ -3025,6 +3036,73 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_
             pt_hit h = wideHit<INST>(S, w, b, tmin, tmax);
             if (PT_TRACE_DIAG_VISITS) h.mat = (int)w.visits;
             hits[ray] = h;
+            ray = -1;
+        }
+    }
+    flushCounters(counters, c);
+}
+
+// pt_render_aov: traceKernelWideQ's walk (the same queue and steps) of the camera rays through the
+// pixel centres of a film's rows, made from the pixel index instead of loaded, over [0.001, inf); the
+// result is the pixel's three 16-byte guide rows {albedo, depth}{n, obj}{p, mat} (include/pt.h, pt_aov)
+// instead of a pt_hit.  The camera waits in LDS and is read where a lane takes a pixel: held in SGPRs across
+// the walk's loop its 18 words would not fit beside the walk's own (the trace kernels use all 102).
+struct AovCam {
+    float pos[3], ll[3], hor[3], ver[3];
+    float invW, invH;
+    int width, stripe_h, nparts, part;
+};
+constexpr int kAovCamWords = sizeof(AovCam) / 4;
+template <int STACK, bool INST>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_TRACE_WAVES))) void aovKernelWideQ(DevScene S, AovCam cam, int64_t n,
+                                                          float4* out, unsigned long long* counters) {
+    __shared__ uint32_t stk[STACK * kWave];
+    const int lane = threadIdx.x;
+    uint32_t* my = stk + lane;
+    const __amdgpu_buffer_rsrc_t nodeRsrc = rawRsrc(S.wnodes);
+    __shared__ uint32_t camWords[kAovCamWords];
+    if (lane < kAovCamWords) camWords[lane] = reinterpret_cast<const uint32_t*>(&cam)[lane];
+    __syncthreads();
+    const volatile uint32_t* cw = camWords;   // (volatile: read at each use, not kept in registers across the loop)
+    const auto camF = [&](int i) { return __uint_as_float(cw[i]); };
+    const float tmin = 0.001f, tmax = __builtin_inff();
+    Counters c{0, 0, 0, 0};
+    int64_t ray = -1, poolBase = 0;
+    uint32_t poolLeft = 0u;
+    bool more = true;
+    WideWalk w = {};
+    WideBest b = {0.0f, 0.0f, -1, false};
+    for (;;) {
+        bool took = false;
+        PT_TRACE_REFILL(took);
+        if (__ballot(ray >= 0) == 0) break;
+        if (ray < 0) continue;
+        if (took) {
+            const int width = (int)cw[14];
+            const int lrow = (int)(ray / width), col = (int)(ray - (int64_t)lrow * width);
+            const float u = ((float)col + 0.5f) * camF(12);
+            const float v = ((float)globalRow(lrow, (int)cw[15], (int)cw[16], (int)cw[17]) + 0.5f) * camF(13);
+            const float3 pos = f3(camF(0), camF(1), camF(2));
+            const float3 d = sub(add(add(f3(camF(3), camF(4), camF(5)), scale(u, f3(camF(6), camF(7), camF(8)))),
+                                     scale(v, f3(camF(9), camF(10), camF(11)))), pos);
+            const pt_ray r = {{pos.x, pos.y, pos.z}, {d.x, d.y, d.z}};
+            wideStartClosest<INST>(S, r, tmin, tmax, w, b, c);
+        }
+        wideGroupClosest<INST>(S, w, b, c);
+        if (wideStep<STACK, INST>(S, nodeRsrc, my, b.closest, w, c)) {
+            HitRec x;
+            float t;
+            float4 r0 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+            float4 r1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1)), r2 = r1;
+            if (wideHitRec<INST>(S, w, b, tmin, tmax, x, t)) {
+                if (x.type == PT_LAMBERTIAN || x.type == PT_METAL) { r0.x = x.m0.x; r0.y = x.m0.y; r0.z = x.m0.z; }
+                else if (x.type == PT_EMISSIVE) { r0.x = fminf(x.m0.x, 1.0f); r0.y = fminf(x.m0.y, 1.0f); r0.z = fminf(x.m0.z, 1.0f); }
+                r0.w = t * sqrtf((w.wd.x * w.wd.x + w.wd.y * w.wd.y) + w.wd.z * w.wd.z);
+                r1 = make_float4(x.n.x, x.n.y, x.n.z, __int_as_float(x.obj));
+                r2 = make_float4(x.p.x, x.p.y, x.p.z, __int_as_float(x.mat));
+            }
+            float4* o = out + 3 * (size_t)ray;
+            o[0] = r0; o[1] = r1; o[2] = r2;
             ray = -1;
         }
     }
@@ -3702,6 +3780,9 @@ struct pt_film {
     DevBuf sums;                  // compat mode: raw per-pixel sample sums of the frame (resolve input)
     DevBuf accum;                 // progressive rendering: fp32 RGB running sums of every accumulated frame
     DevBuf staging;               // device copy of a host output frame
+    DevBuf aovStaging;            // pt_render_aov: device copy of a host output
+    DevBuf dnA, dnB;              // pt_film_denoise: the passes' two scratch images, allocated at first use and kept
+    DevBuf dnRgb, dnAov;          // pt_film_denoise with host pointers: device copies of the image (in, then out) and the guides
     int64_t accumSamples = 0;     // samples per pixel in `accum`
     int cus = 0;                  // compute units of the device (persistent grid size)
     // The last render's work counters (rays, visits, tests, paths, error word), filled by its
@@ -4177,6 +4258,18 @@ int dispatchTrace(int stack, bool wide, const DevScene& S, const pt_ray* r, int6
     if (!ok)   // (the texts of the former tables: "instanced" only ever appeared on the grid-stride path)
         return fail(PT_ERR_STATE, !wide ? "unsupported BVH depth"
                                         : stride && S.winst ? "unsupported instanced BVH depth" : "unsupported wide BVH depth");
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+// pt_render_aov: the queued wide kernel over the film's n pixels.
+int dispatchAov(int stack, const DevScene& S, const AovCam& cam, int64_t n, float4* out, unsigned long long* cnt,
+                hipStream_t st) {
+    const bool ok = withWideStack(stack, [&](auto N) {
+        constexpr int K = decltype(N)::value;
+        const auto launch = [&](auto* kernel) { kernel<<<queryBlocks(n), kWave, 0, st>>>(S, cam, n, out, cnt); };
+        launch(S.winst ? aovKernelWideQ<K, true> : aovKernelWideQ<K, false>);
+    });
+    if (!ok) return fail(PT_ERR_STATE, "unsupported wide BVH depth");
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
@@ -4964,6 +5057,112 @@ int pt_film_set_rng(pt_film* f, const uint32_t* states) {
     for (int64_t i = 0; i < np; i++)
         for (int w = 0; w < 6; w++) soa[(size_t)w * np + i] = states[6 * i + w];
     if (np) HIP_TRY(hipMemcpy(f->state.p, soa.data(), np * 24, hipMemcpyHostToDevice));
+    return PT_OK;
+}
+
+int pt_render_aov(pt_scene* s, pt_film* f, const pt_camera* cam, pt_aov* out, int on_dev, void* stream,
+                  pt_stats* stats) {
+    static_assert(sizeof(pt_aov) == 48, "pt_aov: three 16-byte rows");
+    if (!s || !f || !cam || !out) return fail(PT_ERR_INVALID, "pt_render_aov: null argument");
+    if (!s->built) return fail(PT_ERR_STATE, "pt_render_aov: BVH not built");
+    if (s->device != f->device) return fail(PT_ERR_INVALID, "pt_render_aov: scene and film on different devices");
+    int rc = setDevice(s->device);
+    if (rc || (rc = ensureWide(s))) return rc;   // (first use: builds the tree)
+    hipStream_t st = on_dev ? (hipStream_t)stream : 0;
+    const int64_t np = f->npix;
+    void* dst = out;
+    if (!on_dev) {
+        if ((rc = devReserve(f->aovStaging, (size_t)std::max<int64_t>(1, np) * sizeof(pt_aov)))) return rc;
+        dst = f->aovStaging.p;
+    }
+    AovCam c;
+    for (int a = 0; a < 3; a++) {
+        c.pos[a] = cam->origin[a];
+        c.ll[a] = cam->lower_left[a];
+        c.hor[a] = cam->horizontal[a];
+        c.ver[a] = cam->vertical[a];
+    }
+    c.invW = 1.0f / (float)f->width;
+    c.invH = 1.0f / (float)f->height;
+    c.width = f->width;
+    c.stripe_h = f->stripe_h;
+    c.nparts = f->nparts;
+    c.part = f->part;
+    const bool wait = !on_dev || stats;
+    const int stack = wideStackFor(s->wideDepth);
+    unsigned long long* cnt = s->counters.as<unsigned long long>();
+    StreamGuard guard(st);
+    HIP_TRY(hipMemsetAsync(cnt, 0, kNumCounters * sizeof(unsigned long long), st));
+    if (wait) {
+        HIP_TRY(hipEventCreate(&guard.e0));
+        HIP_TRY(hipEventCreate(&guard.e1));
+        HIP_TRY(hipEventRecord(guard.e0, st));
+    }
+    if (np > 0 && (rc = dispatchAov(stack, devScene(s), c, np, static_cast<float4*>(dst), cnt, st))) return rc;
+    if (!wait) {   // enqueued: nothing is read back (a synchronous call reports a tripped traversal guard)
+        guard.ok = true;
+        return PT_OK;
+    }
+    HIP_TRY(hipEventRecord(guard.e1, st));
+    HIP_TRY(hipEventSynchronize(guard.e1));
+    guard.ok = true;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, guard.e0, guard.e1));
+    unsigned long long k[kNumCounters] = {0};
+    HIP_TRY(hipMemcpy(k, cnt, sizeof(k), hipMemcpyDeviceToHost));
+    k[4] = 0;
+    fillStats(stats, k, ms, true);
+    if (k[7]) return fail(PT_ERR_STATE, "traversal guard tripped (corrupt BVH), flags " + std::to_string(k[7]));
+    if (!on_dev && np > 0) HIP_TRY(hipMemcpy(out, dst, (size_t)np * sizeof(pt_aov), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_film_denoise(pt_film* f, const float* rgb, const pt_aov* aov, float* out, int on_dev, void* stream,
+                    const pt_denoise_opts* opts) {
+    const pt_denoise_opts dflt = {5, 0.6f, 0.1f, 0.02f, {0, 0, 0, 0}};
+    const pt_denoise_opts o = opts ? *opts : dflt;
+    if (o.iterations < 0 || o.iterations > 8) return fail(PT_ERR_INVALID, "pt_film_denoise: iterations must lie in [0, 8]");
+    for (const float sg : {o.sigma_color, o.sigma_albedo, o.sigma_plane})
+        if (!std::isfinite(sg) || !(sg > 0.0f)) return fail(PT_ERR_INVALID, "pt_film_denoise: every sigma must be finite and > 0");
+    if (!f || !rgb || !aov || !out) return fail(PT_ERR_INVALID, "pt_film_denoise: null argument");
+    if (f->nparts != 1) return fail(PT_ERR_INVALID, "pt_film_denoise: the film must own the whole frame (n_parts == 1)");
+    int rc = setDevice(f->device);
+    if (rc) return rc;
+    hipStream_t st = on_dev ? (hipStream_t)stream : 0;
+    const size_t bytes = (size_t)f->npix * 12;
+    const int n = o.iterations;
+    if (n > 1 && (rc = devReserve(f->dnA, bytes))) return rc;
+    if (n > 2 && (rc = devReserve(f->dnB, bytes))) return rc;
+    const float* src = rgb;
+    float* dst = out;
+    if (!on_dev) {
+        if ((rc = devReserve(f->dnRgb, bytes)) || (rc = devReserve(f->dnAov, (size_t)f->npix * sizeof(pt_aov)))) return rc;
+        HIP_TRY(hipMemcpyAsync(f->dnRgb.p, rgb, bytes, hipMemcpyHostToDevice, st));
+        if (n > 0) HIP_TRY(hipMemcpyAsync(f->dnAov.p, aov, (size_t)f->npix * sizeof(pt_aov), hipMemcpyHostToDevice, st));
+        src = dst = f->dnRgb.as<float>();
+        aov = f->dnAov.as<pt_aov>();
+    }
+    StreamWait guard(st);
+    // Pass i reads the previous pass's image and writes a scratch image, A and B in turn; the last pass
+    // writes `dst` -- through A when it would read `dst` itself (one pass, out == rgb).
+    if (n == 0 && dst != src) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
+    if (n == 1 && dst == src && (rc = devReserve(f->dnA, bytes))) return rc;
+    const float isa2 = 1.0f / (o.sigma_albedo * o.sigma_albedo);
+    const float* cur = src;
+    for (int i = 0; i < n; i++) {
+        const float sc = o.sigma_color * (1.0f / (float)(1 << i));   // (exact: a power of two)
+        const float isc2 = 1.0f / (sc * sc);
+        const bool last = i == n - 1;
+        float* to = last && cur != dst ? dst : (i & 1) ? f->dnB.as<float>() : f->dnA.as<float>();
+        HIP_TRY(pt::atrousPass(cur, aov, to, f->width, f->height, 1 << i, isa2, isc2, o.sigma_plane, st));
+        if (last && to != dst) HIP_TRY(hipMemcpyAsync(dst, to, bytes, hipMemcpyDeviceToDevice, st));
+        cur = to;
+    }
+    if (!on_dev) {
+        HIP_TRY(hipMemcpyAsync(out, f->dnRgb.p, bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    guard.ok = true;
     return PT_OK;
 }
 

@@ -3,7 +3,9 @@
 // per-pixel RNG streams, render, quantise and write a PNG.  Runtime flags replace the
 // reference's compile-time constants (global_variables.h:28-35, macros.h:8-12).
 // With --gpus N the frame is split into interleaved row stripes, one host thread per GPU.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +20,7 @@ static void usage() {
                  "usage: pt_render_png [--scene NAME] [--models DIR] [--width W] [--height H] [--spp N]\n"
                  "                     [--depth D] [--seed S] [--gpus N] [--stripe ROWS] [--out FILE]\n"
                  "                     [--rng compat|sample] [--frames K] [--sky default|black] [--nee] [--mis]\n"
+                 "                     [--denoise] [--denoise-sigma X]\n"
                  "--frames K: progressive rendering, K frames of --spp samples accumulated per pixel (the\n"
                  "            headless counterpart of the reference's interactive loop); PNG of the last one\n"
                  "--sky: the sky the scene is rendered under; without it the preset's own (pt_preset_sky):\n"
@@ -27,6 +30,9 @@ static void usage() {
                  "--mis: next-event estimation with multiple importance sampling (PT_RENDER_MIS; implies --nee):\n"
                  "       the light sample and the scatter ray weighted by their pdfs (balance heuristic), so the\n"
                  "       light term next to a lamp is bounded instead of clamped\n"
+                 "--denoise: filter the frame before the PNG (pt_render_aov + pt_film_denoise: the a-trous filter\n"
+                 "       guided by first-hit albedo, normal and position, 5 passes); its colour tolerance is\n"
+                 "       1.2 / sqrt(accumulated samples per pixel) unless --denoise-sigma X gives it; one GPU only\n"
                  "scenes: triangle_world (default, as the reference), random_world, test_world, rtiow,\n"
                  "        cornell, bunny_cornell, bunny_field, cornell_lit, bunny_cornell_lit\n");
 }
@@ -43,7 +49,8 @@ static void usage() {
 int main(int argc, char** argv) {
     std::string scene = "triangle_world", models = "models", out = "debug.png", sky;
     int width = 0, height = 0, spp = -1, depth = -1, gpus = 1, stripe = 8, frames = 1, rng = PT_RNG_COMPAT;
-    bool nee = false, mis = false;
+    bool nee = false, mis = false, denoise = false;
+    float denoiseSigma = 0.0f;
     unsigned long long seed = 1;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -64,6 +71,11 @@ int main(int argc, char** argv) {
         else if (a == "--frames") frames = std::atoi(next());
         else if (a == "--nee") nee = true;
         else if (a == "--mis") mis = true;
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-sigma") {
+            denoiseSigma = (float)std::atof(next());
+            if (!(denoiseSigma > 0.0f) || !std::isfinite(denoiseSigma)) { usage(); return 2; }
+        }
         else if (a == "--sky") {
             sky = next();
             if (sky != "default" && sky != "black") { usage(); return 2; }
@@ -75,6 +87,10 @@ int main(int argc, char** argv) {
             else { usage(); return 2; }
         }
         else { usage(); return 2; }
+    }
+    if (denoise && gpus > 1) {   // (the guides of a pixel's taps live on other GPUs: gathering them is out of scope)
+        usage();
+        return 2;
     }
     pt_scene_desc d;
     CHECK(pt_preset_scene(scene.c_str(), models.c_str(), width, height, &d));
@@ -114,19 +130,42 @@ int main(int argc, char** argv) {
             std::vector<int32_t> rows(nrows);
             CHECK(pt_film_rows(f, rows.data()));
             std::vector<uint8_t> part((size_t)npix * 4);
+            std::vector<float> rgb(denoise ? (size_t)npix * 3 : 0);   // --denoise: the frame as floats, filtered before it is quantised
             pt_render_opts o{};
             o.rng = rng;
-            o.out_format = PT_OUT_RGBA8;
+            o.out_format = denoise ? PT_OUT_RGB32F : PT_OUT_RGBA8;
             o.flags = (frames > 1 ? PT_RENDER_ACCUMULATE : 0) | (nee ? PT_RENDER_NEE : 0) | (mis ? PT_RENDER_MIS : 0);
             pt_stats st{};
             for (int k = 0; k < frames; k++) {
-                CHECK(pt_render_ex(s, f, &d.camera, d.spp, d.max_depth, reinterpret_cast<float*>(part.data()), 0,
-                                   nullptr, &o, &st));
+                CHECK(pt_render_ex(s, f, &d.camera, d.spp, d.max_depth,
+                                   denoise ? rgb.data() : reinterpret_cast<float*>(part.data()), 0, nullptr, &o, &st));
                 kms[g] += st.kernel_ms;
                 stats[g].rays += st.rays;
                 if (frames > 1 && g == 0)
                     std::printf("frame %d: %d spp accumulated, %.2f ms kernel on GPU 0\n", k + 1, (k + 1) * d.spp,
                                 st.kernel_ms);
+            }
+            if (denoise) {   // (one GPU, the whole frame) the guides, the filter, then PngImage::saveColor's quantisation
+                std::vector<pt_aov> aov((size_t)npix);
+                pt_stats ast{};
+                CHECK(pt_render_aov(s, f, &d.camera, aov.data(), 0, nullptr, &ast));
+                int64_t samples = (int64_t)frames * d.spp;
+                if (frames > 1) CHECK(pt_film_accumulated(f, &samples));
+                pt_denoise_opts dn{};
+                dn.iterations = 5;
+                dn.sigma_color = denoiseSigma > 0.0f ? denoiseSigma : (float)(1.2 / std::sqrt((double)std::max<int64_t>(1, samples)));
+                dn.sigma_albedo = 0.1f;
+                dn.sigma_plane = 0.02f;
+                CHECK(pt_film_denoise(f, rgb.data(), aov.data(), rgb.data(), 0, nullptr, &dn));
+                std::printf("denoised: %lld spp, sigma_color %.4f, AOV pass %.3f ms kernel\n", (long long)samples,
+                            dn.sigma_color, ast.kernel_ms);
+                for (size_t i = 0; i < (size_t)npix; i++) {   // png_image.h:24-30, rows kept in film order
+                    for (int c = 0; c < 3; c++) {
+                        const float v = rgb[3 * i + c];
+                        part[4 * i + c] = (uint8_t)((v < 0.0f ? 0.0f : v > 0.999f ? 0.999f : v) * 256.0f);
+                    }
+                    part[4 * i + 3] = 255;
+                }
             }
             for (int r = 0; r < nrows; r++)
                 std::memcpy(&frame[(size_t)rows[r] * d.width * 4], &part[(size_t)r * d.width * 4], 4 * (size_t)d.width);

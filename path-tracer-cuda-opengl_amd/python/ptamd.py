@@ -33,7 +33,11 @@ HIT_DTYPE = np.dtype([("hit", "<i4"), ("obj", "<i4"), ("mat", "<i4"), ("front_fa
                       ("t", "<f4"), ("p", "<f4", (3,)), ("n", "<f4", (3,))])
 NODE_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("parent", "<i4"), ("objid", "<i4"),
                        ("bmin", "<f4", (3,)), ("bmax", "<f4", (3,))])
+# pt_aov: a pixel's first-hit guides, three 16-byte rows (render_aov, denoise)
+AOV_DTYPE = np.dtype([("albedo", "<f4", (3,)), ("depth", "<f4"), ("n", "<f4", (3,)), ("obj", "<i4"),
+                      ("p", "<f4", (3,)), ("mat", "<i4")])
 assert OBJECT_DTYPE.itemsize == 44 and MATERIAL_DTYPE.itemsize == 24 and HIT_DTYPE.itemsize == 44
+assert AOV_DTYPE.itemsize == 48
 
 
 class Camera(C.Structure):
@@ -55,6 +59,11 @@ class Stats(C.Structure):
 class RenderOpts(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("leaf_batch", C.c_int32), ("shade_batch", C.c_int32), ("flags", C.c_int32),
                 ("rng", C.c_int32), ("chunk", C.c_int32), ("out_format", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class DenoiseOpts(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_plane", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
 RNG_COMPAT, RNG_SAMPLE = 0, 1
@@ -102,7 +111,7 @@ EXPORTS = [
     "pt_scene_build_bvh_ex", "pt_film_stats", "pt_preset_instanced", "pt_instanced_desc_free",
     "pt_scene_create_instanced", "pt_trace_occluded", "pt_trace_occluded_device",
     "pt_scene_update_instances", "pt_scene_set_sky", "pt_preset_sky", "pt_scene_light_count",
-    "pt_scene_download_lights", "pt_scene_download_wide",
+    "pt_scene_download_lights", "pt_scene_download_wide", "pt_render_aov", "pt_film_denoise",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -167,6 +176,8 @@ _sig = {
     "pt_render": (C.c_int, [_P, _P, C.POINTER(Camera), C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(Stats)]),
     "pt_render_ex": (C.c_int, [_P, _P, C.POINTER(Camera), C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(RenderOpts),
                                C.POINTER(Stats)]),
+    "pt_render_aov": (C.c_int, [_P, _P, C.POINTER(Camera), _P, C.c_int, _P, C.POINTER(Stats)]),
+    "pt_film_denoise": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.POINTER(DenoiseOpts)]),
     "pt_film_reset": (C.c_int, [_P, _P]),
     "pt_film_clear": (C.c_int, [_P, _P]),
     "pt_film_accumulated": (C.c_int, [_P, C.POINTER(C.c_int64)]),
@@ -602,3 +613,46 @@ def render(scene: Scene, film: Film, camera: Camera, spp: int, max_depth: int, o
                             C.c_void_p(int(stream) if stream else 0), C.byref(opts), C.byref(st) if wait else None),
            "pt_render_ex")
     return None, (st if wait else None)
+
+
+def render_aov(scene: Scene, film: Film, camera: Camera, out=None, stream=None, wait: bool = True):
+    """pt_render_aov: the first-hit guides (AOV_DTYPE: albedo, depth, n, obj, p, mat) of every pixel of
+    the film's rows, from the camera ray through the pixel centre (no random number, no lens; the
+    film's streams and sums are untouched).  `out` may be a numpy AOV_DTYPE array (host) or an integer
+    device pointer to n_pixels x 48 bytes (then `stream` is a hipStream_t handle or None).  Returns
+    (records or None, Stats); wait=False (device output only) enqueues and returns Stats None."""
+    st = Stats()
+    if out is None or isinstance(out, np.ndarray):
+        rec = np.zeros(film.n_pixels, AOV_DTYPE) if out is None else out
+        assert rec.dtype == AOV_DTYPE and rec.flags["C_CONTIGUOUS"] and rec.size >= film.n_pixels
+        _check(lib.pt_render_aov(scene.h, film.h, C.byref(camera), _ptr(rec), 0, None, C.byref(st)), "pt_render_aov")
+        return rec, st
+    _check(lib.pt_render_aov(scene.h, film.h, C.byref(camera), C.c_void_p(int(out)), 1,
+                             C.c_void_p(int(stream) if stream else 0), C.byref(st) if wait else None), "pt_render_aov")
+    return None, (st if wait else None)
+
+
+def denoise(film: Film, rgb, aov, out=None, stream=None, iterations: int = 5, sigma_color=None,
+            sigma_albedo: float = 0.1, sigma_plane: float = 0.02, spp=None):
+    """pt_film_denoise: the edge-avoiding a-trous filter guided by render_aov's records (pt.h states
+    every operation), for a film that owns its whole frame.  rgb / aov / out are numpy arrays (float32
+    n_pixels x 3, AOV_DTYPE n_pixels; the call is synchronous and returns the filtered image) or integer
+    device pointers (all of them; the passes are enqueued on `stream` and None is returned; out may
+    equal rgb).  sigma_color=None means 1.2 / sqrt(max(1, spp)) -- the colour tolerance shrinks with the
+    frame's noise -- and then `spp`, the frame's samples per pixel, is required."""
+    if sigma_color is None:
+        if spp is None:
+            raise ValueError("denoise: give sigma_color, or spp to derive it from")
+        sigma_color = 1.2 / float(np.sqrt(max(1, spp)))
+    opts = DenoiseOpts(iterations, sigma_color, sigma_albedo, sigma_plane)
+    if isinstance(rgb, np.ndarray):
+        assert isinstance(aov, np.ndarray) and (out is None or isinstance(out, np.ndarray))
+        assert rgb.dtype == np.float32 and rgb.flags["C_CONTIGUOUS"] and rgb.size == film.n_pixels * 3
+        assert aov.dtype == AOV_DTYPE and aov.flags["C_CONTIGUOUS"] and aov.size == film.n_pixels
+        res = np.zeros((film.n_pixels, 3), np.float32) if out is None else out
+        assert res.dtype == np.float32 and res.flags["C_CONTIGUOUS"] and res.size == film.n_pixels * 3
+        _check(lib.pt_film_denoise(film.h, _ptr(rgb), _ptr(aov), _ptr(res), 0, None, C.byref(opts)), "pt_film_denoise")
+        return res
+    _check(lib.pt_film_denoise(film.h, C.c_void_p(int(rgb)), C.c_void_p(int(aov)), C.c_void_p(int(out if out is not None else rgb)),
+                               1, C.c_void_p(int(stream) if stream else 0), C.byref(opts)), "pt_film_denoise")
+    return None
