@@ -168,10 +168,32 @@ struct Xorwow {
 // with key = seed and counter = {s, p_lo, p_hi, "SAMP"} seeds a XORWOW state, whose draws
 // then cost a few shifts each (the reference's generator family, curand_uniform mapping).
 // Any sample of any pixel starts anywhere, in one block of work.
+// PEEL (the step kernels' camera-ray site): rounds 1 and 2 written out with the counter's zero word
+// folded (the loop's trip count hides it from the compiler).  Round 1: c2 = 0, so its product is 0
+// -- no second multiply, n0 = c1 ^ k0, and the next c1 = 0.  Round 2: that zero c1 drops out of n0.
+// The same words as ten loop rounds; the simple kernel keeps the loop alone (the written-out rounds
+// cost it two VGPRs).
+template <bool PEEL = false>
 __device__ __forceinline__ Xorwow sampleStream(uint32_t k0, uint32_t k1, uint32_t sample, uint32_t pixel) {
     uint32_t c0 = sample, c1 = pixel, c2 = 0u, c3 = 0x53414D50u;
-#pragma unroll 2   // (pairs of rounds: no register moves; a full unroll raises the camera-ray site's pressure)
-    for (int r = 0; r < 10; r++) {
+    if constexpr (PEEL) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * sample;
+        const uint32_t a0 = pixel ^ k0, a2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), 0x53414D50u, k1, 0x96);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+        const uint64_t q0 = (uint64_t)0xD2511F53u * a0, q1 = (uint64_t)0xCD9E8D57u * a2;
+        c0 = (uint32_t)(q1 >> 32) ^ k0;
+        c1 = (uint32_t)q1;
+        c2 = __builtin_amdgcn_bitop3_b32((uint32_t)(q0 >> 32), (uint32_t)p0, k1, 0x96);
+        c3 = (uint32_t)q0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    // (the loop alone: pairs of rounds -- no register moves, and a full unroll raised the camera-ray
+    // site's pressure; after the written-out rounds the remaining eight unroll at no register's cost
+    // and drop the loop's counter, compare and four branches per stream)
+#pragma unroll(PEEL ? 8 : 2)
+    for (int r = PEEL ? 2 : 0; r < 10; r++) {
         // one 32 x 32 -> 64 multiply per word (v_mad_u64_u32) instead of mul_hi + mul_lo
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
         const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
@@ -270,6 +292,13 @@ __device__ __forceinline__ uint32_t mul80(uint32_t x) {
     return shlOpaque<6>(x) + (x << 4);
 }
 __device__ __forceinline__ uint32_t mul48(uint32_t x) { return shlOpaque<5>(x) + (x << 4); }   // x < 2^27
+// A wave total (the render kernels' work counters) plus a wave-uniform count, in a scalar register.
+// Written as the instruction: a plain `acc += n` of two uniform values is selected as a v_add_u32
+// on a VGPR accumulator that then lives for the whole kernel (one VALU per update and one of the 96
+// registers per counter), and a readfirstlane around the sum does not change that.
+__device__ __forceinline__ void waveCount(uint32_t& acc, uint32_t n) {
+    asm("s_add_u32 %0, %0, %1" : "+s"(acc) : "s"(n) : "scc");
+}
 __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
     return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
@@ -480,6 +509,27 @@ __device__ __forceinline__ float rcpRNWave(float x, uint64_t hasM) {
     const uint64_t slowM = hasM & __ballot(ex - kRcpExpLo > kRcpExpHi - kRcpExpLo);
     float y = rcpNewton(x);
     if (__builtin_expect(slowM != 0, 0)) y = __builtin_amdgcn_inverse_ballot_w64(slowM) ? 1.0f / x : y;
+    return y;
+}
+// A ray direction's three reciprocals with one range check for the wave (the wide kernels' ray
+// start): rcpRN per component costs a compare, an exec save / restore and a branch around the
+// division each.  rcpKey moves the biased exponent to the top byte and turns it by 255 - kRcpExpHi,
+// so the exponents outside [kRcpExpLo, kRcpExpHi] are the keys below kRcpKeyLim; the smallest of the
+// three keys is balloted (among the lanes that run this: the caller's exec mask), and the wave takes
+// the IEEE divisions when any lane needs one.  Per lane and component the value is rcpRN's: the
+// division exactly where rcpRN divides.
+constexpr uint32_t kRcpKeyLim = (255u - kRcpExpHi + kRcpExpLo) << 24;
+__device__ __forceinline__ uint32_t rcpKey(float x) { return (__float_as_uint(x) << 1) + ((255u - kRcpExpHi) << 24); }
+__device__ __forceinline__ float3 rcpRN3Wave(float3 d) {
+    if constexpr (!PT_FAST_RCP) return f3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    const uint32_t kx = rcpKey(d.x), ky = rcpKey(d.y), kz = rcpKey(d.z);
+    const uint64_t slowM = __ballot(min(min(kx, ky), kz) < kRcpKeyLim);
+    float3 y = f3(rcpNewton(d.x), rcpNewton(d.y), rcpNewton(d.z));
+    if (__builtin_expect(slowM != 0, 0)) {
+        y.x = kx < kRcpKeyLim ? 1.0f / d.x : y.x;
+        y.y = ky < kRcpKeyLim ? 1.0f / d.y : y.y;
+        y.z = kz < kRcpKeyLim ? 1.0f / d.z : y.z;
+    }
     return y;
 }
 __device__ __forceinline__ void wideTestTri(const Prim& q, uint64_t hasM, float3 o, float3 d, float tmin, float& closest,
@@ -812,17 +862,19 @@ __device__ __forceinline__ int traceRefStackless(const DevScene& S, float3 o, fl
 // loads of the shading record are one memory round trip (instead of prim -> normal -> material).
 struct HitRec { float3 p, n; int mat, obj; bool front; float4 m0; float ir; int type; };
 
+// SPH = false: no record is a sphere (the TRI kernels), so the sphere normal is not compiled in.
+// The record's address is a 32-bit byte offset off the uniform base (48 k < 2^32: k < 2^26,
+// pt_scene_create), like the LEAF step's primitive records: no 64-bit multiply.
+template <bool SPH = true>
 __device__ __forceinline__ HitRec makeHitFrom(const float4* shade, int k, float t, float3 o, float3 d) {
     HitRec h;
-    const float4* r = shade + 3 * (size_t)k;
+    const float4* r = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(shade) + mul48((uint32_t)k));
     const float4 s0 = r[0], s1 = r[1], s2 = r[2];
     const uint32_t tf = __float_as_uint(s2.y);
     h.p = add(o, scale(t, d));
-    float3 outward;
-    if (tf >> 16) {   // sphere: (p - c) / r
-        outward = divs(sub(h.p, xyz(s0)), s0.w);
-    } else {
-        outward = xyz(s0);
+    float3 outward = xyz(s0);
+    if constexpr (SPH) {
+        if (tf >> 16) outward = divs(sub(h.p, xyz(s0)), s0.w);   // sphere: (p - c) / r
     }
     h.front = dot3(d, outward) < 0.0f;
     h.n = h.front ? outward : neg(outward);
@@ -1640,7 +1692,19 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     const __amdgpu_buffer_rsrc_t nodeRsrc = rawRsrc(WIDE ? (const void*)S.wnodes : (const void*)S.nodes);
     uint32_t* my = stk + lane;
     // Work counters are wave totals kept in scalar registers: each step adds the popcount of
-    // a ballot of the lanes that did the work (no per-lane counter VGPRs).
+    // a ballot of the lanes that did the work (no per-lane counter VGPRs; waveCount).
+    // The compat unit's kernels (CTU: pt_compat.hip) keep the plain sum.  Those with critical-pixel
+    // waves must: PT_CRIT_TRACE counts inside a per-lane loop that lanes leave at different
+    // iterations, so their counters are per-lane values (lane 0's is reported).  The stack-16 and -24
+    // ones may not: one of them takes two more VGPRs with scalar counters, and CTU also keeps rcpRN
+    // per component at the ray start, where the one-check form costs the triangle-only stack-8
+    // kernel its fifth wave (97 VGPRs).
+    constexpr bool CTU = !SAMPLE && WIDE && !INST;
+#define PT_COUNT(v, x)                                                                              \
+    do {                                                                                          \
+        if constexpr (CTU) (v) += (x);                                                            \
+        else waveCount((v), (x));                                                                 \
+    } while (0)
     uint32_t sRays = 0, sVisits = 0, sTris = 0, sSph = 0, sPaths = 0;
 #ifdef PT_DIAG
     uint32_t itN = 0, itL = 0, itS = 0, sPops = 0, sRedo = 0;   // scheduler diagnostics (iterations per kind)
@@ -1706,7 +1770,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         qn = 0;                                                                                   \
         if constexpr (CRITK) pxRays++;                                                            \
         if constexpr (WIDE) {   /* the root is slot 0 of a virtual node at base 0 */              \
-            inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));                                         \
+            if constexpr (CTU) inv = f3(rcpRN(d.x), rcpRN(d.y), rcpRN(d.z));                      \
+            else inv = rcpRN3Wave(d);                                                             \
             const uint32_t oc_ = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u); \
             oct = oc_;                                                                            \
             tg = 0u;                                                                              \
@@ -1760,12 +1825,12 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 const float4* w_ = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(S.wprims) + mul48(k_)); \
                 const Prim q_{w_[0], w_[1], w_[2]};                                               \
                 if constexpr (TRI) {   /* (no record is a sphere) */                              \
-                    sTris += (uint32_t)__popcll(__ballot(true));                                  \
+                    PT_COUNT(sTris, (uint32_t)__popcll(__ballot(true)));                          \
                     wideTestTri(q_, __ballot(true), o, d, 0.001f, closest, best, bestLo);         \
                 } else {                                                                          \
                 const bool isS_ = __float_as_uint(q_.p2.w) != 0u;                                 \
-                sTris += (uint32_t)__popcll(__ballot(!isS_));                                     \
-                sSph += (uint32_t)__popcll(__ballot(isS_));                                       \
+                PT_COUNT(sTris, (uint32_t)__popcll(__ballot(!isS_)));                             \
+                PT_COUNT(sSph, (uint32_t)__popcll(__ballot(isS_)));                               \
                 if (sph_) wideTest<true>(q_, o, d, inv, 0.001f, closest, best, bestLo, lb_, redo_, 0u); \
                 else if (INST) wideTest<false>(q_, o, d, inv, 0.001f, closest, best, bestLo, lb_, redo_, 0u); \
                 else wideTestTri(q_, __ballot(true), o, d, 0.001f, closest, best, bestLo);   /* (SHADE decides) */ \
@@ -1780,7 +1845,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             const uint32_t child_ = (ng >> 8) + (bit_ ^ (oct & 7u));                              \
             ng &= ~(1u << bit_);                                                                  \
             if (ng & 0xffu) { my[sp * kWave] = ng; sp++; }   /* sp < depth <= STACK (host check) */ \
-            sVisits += (uint32_t)__popcll(__ballot(true));                                        \
+            PT_COUNT(sVisits, (uint32_t)__popcll(__ballot(true)));                                \
             const uint32_t off_ = mul80(child_);                                                  \
             const uint4 n0_ = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off_, 0, 0)); \
             const uint4 n1_ = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(nodeRsrc, off_ + 16u, 0, 0)); \
@@ -1848,7 +1913,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             needTaskM &= ~((took_ & ~left_) | in_);                                               \
             got |= in_;                                                                           \
             if (laneOf(in_)) {                                                                    \
-                const uint32_t s0_ = (hi_ ? blkB_ : blkA_) * (uint32_t)Q_.span;                   \
+                /* (both groups' first samples are wave-uniform: scalar products, one select) */  \
+                const uint32_t sA_ = blkA_ * (uint32_t)Q_.span, sB_ = blkB_ * (uint32_t)Q_.span;  \
+                const uint32_t s0_ = hi_ ? sB_ : sA_;                                             \
                 taskState[lane] = make_uint4((uint32_t)c_ | ((uint32_t)r_ << 16), s0_,             \
                                              min(s0_ + (uint32_t)Q_.span, (uint32_t)Q_.spp), 0u); \
                 sum = f3(0.0f, 0.0f, 0.0f);                                                       \
@@ -1861,7 +1928,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     // are live, measured 2.6 % slower); the caller moves the lane's bit to needTaskM.
 #define PT_FINISH_TASK(ts)                                                                          \
     do {                                                                                          \
-        unsigned long long* acc_ = kargs()->pixAcc + 4 * (size_t)(((ts).x >> 16) * (uint32_t)kargs()->width + ((ts).x & 0xffffu)); \
+        /* (a 24-bit multiply-add: sample mode's local rows and width are < 2^16, launchRender) */ \
+        unsigned long long* acc_ = kargs()->pixAcc + 4 * (size_t)(__umul24((ts).x >> 16, (uint32_t)kargs()->width) + ((ts).x & 0xffffu)); \
         addBlock(acc_, sum, (ts).w + 1u, kargs()->measureCost != 0);                              \
     } while (0)
     // New camera sample: main.cu:284-286 + camera::get_ray (lens sample: lensOffset; time draw skipped).
@@ -1874,7 +1942,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             const uint32_t grow_ = (uint32_t)globalRowFast((int)(ts_.x >> 16), Q_.stripe_h, Q_.stripeShift, \
                                                            Q_.nparts, Q_.part);                  \
             frow = (float)grow_;                                                                  \
-            g = sampleStream(Q_.seed0, Q_.seed1, Q_.sampleBase + ts_.y,                           \
+            g = sampleStream<true>(Q_.seed0, Q_.seed1, Q_.sampleBase + ts_.y,                     \
                              grow_ * (uint32_t)Q_.width + (ts_.x & 0xffffu));                      \
         }                                                                                         \
         const float u_ = (fcol + g.uniform()) * Q_.invW;                                           \
@@ -1936,9 +2004,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         }
     }
     activeM = __ballot(started);   // (once per wave)
-    sRays += (uint32_t)__popcll(activeM);
-    sPaths += (uint32_t)__popcll(activeM) +
-              (!SAMPLE && P.max_depth <= 0 ? (uint32_t)__popcll(__ballot(valid)) * (uint32_t)nSamples : 0u);
+    PT_COUNT(sRays, (uint32_t)__popcll(activeM));
+    PT_COUNT(sPaths, (uint32_t)__popcll(activeM) +
+                                 (!SAMPLE && P.max_depth <= 0 ? (uint32_t)__popcll(__ballot(valid)) * (uint32_t)nSamples : 0u));
 
     for (;;) {
 #ifdef PT_DIAG
@@ -1978,7 +2046,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 
         if (kind == 0) {
             // ------------------------------------------------------------------ NODE
-            sVisits += (uint32_t)nN;
+            PT_COUNT(sVisits, (uint32_t)nN);
             PT_DIAG_ADD(itN, 1u);
             const bool wantNode = laneOf(mN);
             if constexpr (WIDE) {
@@ -2187,14 +2255,14 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 if constexpr (TRI) {   // (the triangle-only branch below, alone)
                     wideTestTri(q0, mL, o, d, 0.001f, closest, best, bestLo);
                     wideTestTri(q1, m1, o, d, 0.001f, closest, best, bestLo);
-                    sTris += (uint32_t)nL + (uint32_t)__popcll(m1);
+                    PT_COUNT(sTris, (uint32_t)nL + (uint32_t)__popcll(m1));
                 } else if (kargs()->S.hasSpheres) {   // (uniform: read where needed)
                     if (h0) wideTest<true>(q0, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
                     if (h1) wideTest<true>(q1, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
                     const uint64_t s0 = mL & __ballot(__float_as_uint(q0.p2.w) != 0u);
                     const uint64_t s1 = m1 & __ballot(__float_as_uint(q1.p2.w) != 0u);
-                    sTris += (uint32_t)nL + (uint32_t)__popcll(m1) - (uint32_t)__popcll(s0) - (uint32_t)__popcll(s1);
-                    sSph += (uint32_t)__popcll(s0) + (uint32_t)__popcll(s1);
+                    PT_COUNT(sTris, (uint32_t)nL + (uint32_t)__popcll(m1) - (uint32_t)__popcll(s0) - (uint32_t)__popcll(s1));
+                    PT_COUNT(sSph, (uint32_t)__popcll(s0) + (uint32_t)__popcll(s1));
                 } else {
                     if constexpr (INST) {
                         if (h0) wideTest<false>(q0, o, d, inv, 0.001f, closest, best, bestLo, lb, redo, kh);
@@ -2203,7 +2271,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                         wideTestTri(q0, mL, o, d, 0.001f, closest, best, bestLo);
                         wideTestTri(q1, m1, o, d, 0.001f, closest, best, bestLo);
                     }
-                    sTris += (uint32_t)nL + (uint32_t)__popcll(m1);
+                    PT_COUNT(sTris, (uint32_t)nL + (uint32_t)__popcll(m1));
                 }
                 if (redo) oct |= 8u;   // order-dependent candidate: repeat the query in the reference's order
                 if (SPEC && tg == 0u && (oct & 48u)) {   // this group is done: the last parked one is next
@@ -2251,8 +2319,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                     }
                 }
             }
-            sTris += (uint32_t)__popcll(__ballot(tested && !sph));
-            sSph += (uint32_t)__popcll(__ballot(tested && sph));
+            PT_COUNT(sTris, (uint32_t)__popcll(__ballot(tested && !sph)));
+            PT_COUNT(sSph, (uint32_t)__popcll(__ballot(tested && sph)));
             }
             }
         }
@@ -2275,7 +2343,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 if constexpr (!TRI) triScene = !kargs()->S.hasSpheres;
                 if (triScene && S.nprims > 1) {
                     if (shading && best >= 0 && !redo) {
-                        const float4* bx = kargs()->S.wbox + 2 * (size_t)best;
+                        // (a 32-bit byte offset: 32 best < 2^31, < 2^26 primitives)
+                        const float4* bx = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(kargs()->S.wbox) +
+                                                                           ((uint32_t)best << 5));
                         redo = deferredRedo(bx[0], *reinterpret_cast<const float2*>(bx + 1), o, inv, closest, bestLo);
 #ifdef PT_DIAG
                         {   // (which of them because the ray misses the final hit's box outright)
@@ -2323,7 +2393,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 } else {
                     int objI_;
                     HitRec h = INST ? makeHitInst(ldScene(kargs()), (uint32_t)best & kPrimMask, closest, o, d, objI_)
-                                    : (WIDE ? makeHitFrom(kargs()->S.wshade, best & (int)kPrimMask, closest, o, d)
+                                    : (WIDE ? makeHitFrom<!TRI>(kargs()->S.wshade, best & (int)kPrimMask, closest, o, d)
                                             : makeHit(S, best, closest, o, d));
                     if (!scatterInto(h, d, att, g)) {
                         if constexpr (LIT) contrib = emitted(h, att);
@@ -2414,8 +2484,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
             const unsigned long long tS4 = __builtin_amdgcn_s_memtime();
             cycSh += tS1 - tK0; cycTk += tS2 - tS1; cycNp += tS3 - tS2; cycBr += tS4 - tS3;
 #endif
-            sRays += (uint32_t)__popcll(newRayM);
-            sPaths += (uint32_t)__popcll(newSampleM);
+            PT_COUNT(sRays, (uint32_t)__popcll(newRayM));
+            PT_COUNT(sPaths, (uint32_t)__popcll(newSampleM));
         }
 #ifdef PT_DIAG
         {   // shader-clock cycles per step kind (the step's memory waits included)
@@ -2477,6 +2547,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #undef PT_TAKE_TASKS
 #undef PT_FINISH_TASK
 #undef PT_DIAG_ADD
+#undef PT_COUNT
 
 #ifdef PT_TU_COMPAT
 }  // namespace
