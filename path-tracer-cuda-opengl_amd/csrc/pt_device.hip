@@ -939,13 +939,18 @@ __device__ __forceinline__ HitRec makeHitInst(const DevScene& S, uint32_t key, f
 
 // ------------------------------------------------------------------------ BSDFs
 // utility.h:51-62 / 73-82; vec3(...) arguments drawn x, y, z in order.
+// (trials: PT_DIAG builds count the lane's trials there; unused otherwise)
 template <class G>
-__device__ __forceinline__ float3 onUnitSphere(G& g) {
+__device__ __forceinline__ float3 onUnitSphere(G& g, uint32_t* trials = nullptr) {
     float3 res;
     float norm;
+    (void)trials;
     do {   // draws x, y, z in order; centered2() = 2 * (uniform() - 0.5f) exactly
         res = g.centered2x3();
         norm = len2(res);
+#ifdef PT_DIAG
+        if (trials) ++*trials;
+#endif
     } while (norm >= 1.0f);
     return divs(res, sqrtf(norm));
 }
@@ -1013,11 +1018,11 @@ __device__ __forceinline__ bool scatter(const DevScene& S, const HitRec& h, floa
 // dielectric's (1, 1, 1) is skipped, exactly (x * 1.0f == x for the finite attenuations of a
 // path), and no attenuation value has to live across the material switch.
 template <class G>
-__device__ __forceinline__ bool scatterInto(const HitRec& h, float3& d, float3& att, G& g) {
+__device__ __forceinline__ bool scatterInto(const HitRec& h, float3& d, float3& att, G& g, uint32_t* trials = nullptr) {
     const float4 m0 = h.m0;
     const int type = h.type;
     if (type == PT_LAMBERTIAN) {
-        float3 dir = add(h.n, onUnitSphere(g));
+        float3 dir = add(h.n, onUnitSphere(g, trials));
         if (fabsf(dir.x) < 1e-7f && fabsf(dir.y) < 1e-7f && fabsf(dir.z) < 1e-7f) dir = h.n;
         d = dir;
         att = mul(att, xyz(m0));
@@ -1238,6 +1243,10 @@ struct RenderParams {
     // Flat wide launches: the kernels' TRI instantiations (a triangle-only scene whose edge-form
     // records S.wprims holds, and PT_WIDE_TRI not 0).  Read by the launchers, not by the kernels.
     int tri;
+    // Flat wide sample launches without NEE: the kernels' AHEAD instantiations (with tri; no metal or
+    // dielectric material, a pinhole camera, a stack of 8 or 16, and PT_SHADE_AHEAD not 0).  Read by
+    // the launchers, not by the kernels.
+    int ahead;
 };
 template <bool LIT>
 __device__ __forceinline__ float3 skyOf(const RenderParams& P, float3 d, float3 att) {
@@ -1604,8 +1613,15 @@ __device__ __forceinline__ float3 skyK(float3 d, float3 att) {
 // when the launch is enqueued (RenderParams::tri): the tests of that flag are compile-time here, and
 // the sphere paths (wideTest<true>, the sphere counters, the window form of bestLo) are not compiled
 // into the step loop.  TRI = false is the kernel for every scene, the flag read at run time.
+// AHEAD (with SAMPLE, WIDE, TRI; not NEE): no material of the scene is metal or dielectric and the camera
+// is a pinhole (RenderParams::ahead), so between its two camera draws and the end of its path a sample's
+// XORWOW stream is read by the unit-sphere rejection loop alone: the k-th vector that loop accepts is the
+// k-th scatter's vector whenever it is drawn.  The SHADE step runs one trial loop for the wave, only as
+// long as a lane that scatters now has no vector; every other lane on a path draws along and keeps an
+// accepted vector (unnormalised) in a one-entry LDS slot for its next scatter.  The metal, dielectric and
+// lens code is not compiled in.
 template <int STACK, bool SAMPLE, bool WIDE, bool INST = false, bool LIT = false, bool NEE = false, bool MIS = false,
-          bool TRI = false>
+          bool TRI = false, bool AHEAD = false>
 // (NEE on the deeper wide stacks, 16 and 24 entries: 4 waves per SIMD instead of 5 -- at 96 VGPRs the
 // SHADE step's light sample spilled 1-3 registers, and the 24-entry stack's 6 KB of LDS with the
 // 2.5 KB of NEE state fit 4 waves anyway)
@@ -1613,6 +1629,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     static_assert(!NEE || (WIDE && LIT), "NEE: the wide kernels' LIT instantiations only");
     static_assert(!MIS || NEE, "MIS: the NEE instantiations only");
     static_assert(!TRI || (WIDE && !INST), "TRI: the flat wide kernels only");
+    static_assert(!AHEAD || (SAMPLE && WIDE && !INST && !NEE), "AHEAD: the flat wide sample kernels without NEE only");
     // Deep trees (binary kernels) keep 32 stack entries per lane in LDS (8 KB per wave: 5 waves
     // per SIMD) and the rare deeper entries in global memory (stackSpill, per wave slot and lane).
     constexpr int LS = kLdsStack<STACK, SAMPLE, WIDE>;
@@ -1636,6 +1653,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     // carried through every NODE and LEAF step.  MIS: [9] the scatter ray's pdf (pbs).
     __shared__ float neeV[NEE ? (MIS ? 10 : 9) * kWave : 1];
     __shared__ uint32_t neeF[NEE ? kWave : 1];
+    // AHEAD: the lane's pre-drawn scatter vector (the accepted, unnormalised centered2x3() triple);
+    // haveM says whose slot is full.  Touched by SHADE steps only.
+    __shared__ float aheadV[AHEAD ? 3 * kWave : 1];
     const int lane = threadIdx.x;
     // compat mode: all spp of a pixel in order (its per-pixel XORWOW stream); one wave = one tile
     // (the longest tiles split, below).
@@ -1713,6 +1733,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     unsigned long long sHalf = 0, sParkT = 0;    // LEAF (wide): lanes testing one primitive; tests in parked groups
     unsigned long long cycN = 0, cycL = 0, cycS = 0, cycH = 0;   // and shader cycles per kind, loop head
     unsigned long long cycSh = 0, cycTk = 0, cycNp = 0, cycBr = 0;   // SHADE: shading, tasks, new path, ray start
+    unsigned long long sTrials = 0;   // SHADE: iterations of the unit-sphere trial loop (the wave's, per step)
 #define PT_DIAG_ADD(v, x) (v) += (x)
 #else
 #define PT_DIAG_ADD(v, x) ((void)0)
@@ -1744,6 +1765,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
     // v_cmp_ne) to rebuild a mask that already exists, so only plain integer compares are balloted.
     const uint64_t allM = __ballot(true);
     uint64_t activeM = 0;   // lanes on a path
+    uint64_t haveM = 0;     // AHEAD: lanes whose slot holds their path's next scatter vector
     // sample mode task state: summation block, its tile (cost accounting), rays traced for it
     uint32_t depthPaths = 0;
     uint32_t pxRays = 0;   // compat tile / critical lanes: rays traced for the lane's pixel (P.pixRays)
@@ -1949,7 +1971,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         const float v_ = (frow + g.uniform()) * Q_.invH;                                           \
         o = ld3(Q_.cam.pos);                                                                            \
         d = sub(add(add(ld3(Q_.cam.ll), scale(u_, ld3(Q_.cam.hor))), scale(v_, ld3(Q_.cam.ver))), ld3(Q_.cam.pos));       \
-        if (Q_.cam.lens != 0.0f) lensOffset(ld3(Q_.cam.right), ld3(Q_.cam.up), Q_.cam.lens, g, o, d); \
+        if (!AHEAD && Q_.cam.lens != 0.0f) lensOffset(ld3(Q_.cam.right), ld3(Q_.cam.up), Q_.cam.lens, g, o, d); \
         att = f3(1.0f, 1.0f, 1.0f);                                                               \
         depthLeft = Q_.max_depth;                                                                  \
         if constexpr (NEE) {   /* no direct term yet, no flag */                                  \
@@ -2369,123 +2391,251 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
                 }
             }
             PT_DIAG_ADD(itS, 1u);
-            bool done = false;   // the lane's sample is complete
-            bool shadowNow = false;   // NEE: the lane's next query is a shadow ray
-            if (shading) {
-                float3 contrib = f3(0.0f, 0.0f, 0.0f);
-                bool wasShadow = false;
-                if constexpr (NEE) {
-                    if (shadowQ) {   // the shadow query is complete: its term if nothing was hit, then the parked scatter ray
-                        if (best < 0) {
-                            neeV[0 * kWave + lane] += neeV[3 * kWave + lane];
-                            neeV[1 * kWave + lane] += neeV[4 * kWave + lane];
-                            neeV[2 * kWave + lane] += neeV[5 * kWave + lane];
-                        }
-                        d = f3(neeV[6 * kWave + lane], neeV[7 * kWave + lane], neeV[8 * kWave + lane]);
-                        neeF[lane] = nf & ~1u;
-                        wasShadow = true;
-                    }
-                }
-                if (wasShadow) {
-                } else if (best < 0) {
-                    contrib = PT_SKY();
+#ifdef PT_DIAG
+            uint32_t nTrials = 0u;   // the lane's trials of the unit-sphere loop in this step
+#endif
+            if constexpr (AHEAD) {
+                // A. Classify.  A miss, an emitter or an absorbing type ends the sample; a Lambertian hit
+                // scatters: att *= albedo, o = the hit point, and d holds the shading normal until D adds
+                // the unit vector (the ray's old direction is dead once `front` is known).
+                bool done = false;
+                if (shading) {
+                    float3 contrib = f3(0.0f, 0.0f, 0.0f);
                     done = true;
-                } else {
-                    int objI_;
-                    HitRec h = INST ? makeHitInst(ldScene(kargs()), (uint32_t)best & kPrimMask, closest, o, d, objI_)
-                                    : (WIDE ? makeHitFrom<!TRI>(kargs()->S.wshade, best & (int)kPrimMask, closest, o, d)
-                                            : makeHit(S, best, closest, o, d));
-                    if (!scatterInto(h, d, att, g)) {
-                        if constexpr (LIT) contrib = emitted(h, att);
-                        if constexpr (NEE) {   // the light was sampled at the hit this ray left
-                            // (instanced: the hit key's low gBits bits are the shading index)
-                            const int sk = INST ? best & ((1 << kargs()->S.gBits) - 1) : best & (int)kPrimMask;
-                            if ((nf & 2u) && sampledLight(kargs()->S.wshade, sk, h)) {
-                                if constexpr (MIS && INST)
-                                    contrib = emittedWeightedAt(kargs()->lights,
-                                                                instLightSlot(kargs()->instLightFirst, kargs()->lightSlot,
-                                                                              (uint32_t)best & kPrimMask, kargs()->S.gBits),
-                                                                kargs()->nLights, closest, d, neeV[9 * kWave + lane], contrib);
-                                else if constexpr (MIS)
-                                    contrib = emittedWeighted(kargs()->lights, kargs()->lightSlot, kargs()->nLights, h.obj,
-                                                              closest, d, neeV[9 * kWave + lane], contrib);
-                                else contrib = f3(0.0f, 0.0f, 0.0f);
+                    if (best < 0) {
+                        contrib = PT_SKY();
+                    } else {   // makeHitFrom's record, of which a Lambertian-only scene needs the normal, the albedo and the type
+                        const float4* r = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(kargs()->S.wshade) +
+                                                                          mul48((uint32_t)(best & (int)kPrimMask)));
+                        const float4 s0 = r[0], s1 = r[1];
+                        const uint32_t tf = __float_as_uint(r[2].y);
+                        if ((tf & 0xffffu) == (uint32_t)PT_LAMBERTIAN) {
+                            const float3 p = add(o, scale(closest, d));
+                            float3 outward = xyz(s0);
+                            if constexpr (!TRI) {
+                                if (tf >> 16) outward = divs(sub(p, xyz(s0)), s0.w);   // sphere: (p - c) / r
                             }
-                        }
-                        done = true;
-                    } else {
-                        o = h.p;
-                        if (depthLeft == 0) { contrib = PT_SKY(); done = true; }
-                        else if constexpr (NEE) {
-                            nf &= ~2u;
-                            if (h.type == PT_LAMBERTIAN) {
-                                nf |= 2u;
-                                float3 w, term;
-                                if constexpr (MIS) neeV[9 * kWave + lane] = scatterPdf(h.n, d);
-                                if (lightSample<MIS>(kargs()->lights, kargs()->nLights, o, h.n, att, g, w, term)) {
-                                    neeV[3 * kWave + lane] = term.x; neeV[4 * kWave + lane] = term.y; neeV[5 * kWave + lane] = term.z;
-                                    neeV[6 * kWave + lane] = d.x; neeV[7 * kWave + lane] = d.y; neeV[8 * kWave + lane] = d.z;
-                                    d = w;
-                                    nf |= 1u;
-                                    shadowNow = true;
-                                }
-                            }
-                            neeF[lane] = nf;
+                            const bool front = dot3(d, outward) < 0.0f;
+                            o = p;
+                            d = front ? outward : neg(outward);
+                            att = mul(att, xyz(s1));
+                            done = false;
+                        } else if constexpr (LIT) {
+                            if ((tf & 0xffffu) == (uint32_t)PT_EMISSIVE) contrib = mul(att, xyz(s1));
                         }
                     }
+                    if (done) sum = add(sum, contrib);
                 }
-                if (done) {
-                    if constexpr (NEE)
-                        contrib = neeTotal(f3(neeV[0 * kWave + lane], neeV[1 * kWave + lane], neeV[2 * kWave + lane]), contrib);
-                    sum = add(sum, contrib);
-                }
-            }
-            // Every lane steps its sample count by `done` (a lane that is not shading by 0; shadeM
-            // masks its stale state): who completed a sample and who its last one comes from two
-            // integer compares, not from predicates joined over the branches above.
-            uint64_t doneM, finM;
-            if constexpr (SAMPLE) {
+                // B. Step the sample, finish tasks, take tasks, new paths: before the loop, so that a fresh
+                // path draws along at once.  Every shading lane either completed its sample or scatters.
                 const uint4 ts = taskState[lane];
                 const uint32_t y1 = ts.y + (done ? 1u : 0u);
                 taskState[lane].y = y1;
-                doneM = shadeM & __ballot(y1 != ts.y);
-                finM = doneM & __ballot(y1 == ts.z);
+                const uint64_t doneM = shadeM & __ballot(y1 != ts.y), finM = doneM & __ballot(y1 == ts.z);
+                const uint64_t scM = shadeM & ~doneM;
                 if (laneOf(finM)) PT_FINISH_TASK(ts);
                 needTaskM |= finM;
-            } else {
-                const int s1 = sample + (done ? 1 : 0);
-                doneM = shadeM & __ballot(s1 != sample);
-                finM = doneM & __ballot(s1 == nSamples);
-                sample = s1;
-            }
-            activeM &= ~finM;
-            // bounce or next sample (newSampleM) for the lanes that go on
-            uint64_t newRayM = shadeM & ~finM, newSampleM = doneM & ~finM;
+                activeM &= ~finM;
+                uint64_t newSampleM = doneM & ~finM, got = 0;
 #ifdef PT_DIAG
-            const unsigned long long tS1 = __builtin_amdgcn_s_memtime();
+                const unsigned long long tS1 = __builtin_amdgcn_s_memtime();
 #endif
-            if constexpr (SAMPLE) {   // idle lanes take new tasks and start their first path
-                uint64_t got = 0;
                 PT_TAKE_TASKS(got);
                 activeM |= got;
-                newRayM |= got;
                 newSampleM |= got;
+#ifdef PT_DIAG
+                const unsigned long long tS2 = __builtin_amdgcn_s_memtime();
+#endif
+                if (laneOf(newSampleM)) PT_NEW_PATH();
+#ifdef PT_DIAG
+                const unsigned long long tS3 = __builtin_amdgcn_s_memtime();
+#endif
+                haveM &= ~(doneM | got);   // (a re-seeded stream: the slot's vector belonged to the old one)
+                // C. One trial loop.  pendM: scatter lanes without a vector -- the loop runs until each of
+                // them has accepted, not at all when there is none.  Every other lane on a path with an
+                // empty slot draws along (a scatter lane whose slot was full empties it in D, so it is one
+                // of them).  A lane leaves at its first acceptance; per trial the wave adds scalar mask
+                // operations only.
+                const uint64_t pendM = scM & ~haveM, hadM = scM & haveM;
+                haveM &= ~scM;
+                const uint64_t drawM = activeM & ~haveM;
+                float3 res = f3(0.0f, 0.0f, 0.0f);
+                float norm = 2.0f;
+                if (pendM != 0 && laneOf(drawM)) {
+                    uint64_t waitM = pendM;
+                    for (;;) {   // draws x, y, z in order, as onUnitSphere does
+                        res = g.centered2x3();
+                        norm = len2(res);
+#ifdef PT_DIAG
+                        nTrials++;
+#endif
+                        waitM &= ~__ballot(norm < 1.0f);
+                        if (norm < 1.0f || waitM == 0) break;
+                    }
+                }
+                // D. Slots, in this LDS order: a scatter lane that had a vector reads it; a lane that drew
+                // along and accepted writes its own.  Then d = n + v / sqrt(len2(v)) with scatterInto's
+                // degenerate-direction rule (len2 recomputed from the stored triple: the same bits).
+                float3 held = f3(0.0f, 0.0f, 0.0f);
+                if (laneOf(hadM)) held = f3(aheadV[0 * kWave + lane], aheadV[1 * kWave + lane], aheadV[2 * kWave + lane]);
+                const uint64_t keepM = drawM & ~pendM & __ballot(norm < 1.0f);
+                if (laneOf(keepM)) {
+                    aheadV[0 * kWave + lane] = res.x; aheadV[1 * kWave + lane] = res.y; aheadV[2 * kWave + lane] = res.z;
+                }
+                haveM |= keepM;
+                if (laneOf(scM)) {
+                    const bool drew = laneOf(pendM);
+                    const float3 v = f3(drew ? res.x : held.x, drew ? res.y : held.y, drew ? res.z : held.z);
+                    const float3 dir = add(d, divs(v, sqrtf(len2(v))));
+                    const bool tiny = fabsf(dir.x) < 1e-7f && fabsf(dir.y) < 1e-7f && fabsf(dir.z) < 1e-7f;
+                    d = f3(tiny ? d.x : dir.x, tiny ? d.y : dir.y, tiny ? d.z : dir.z);
+                }
+                // A scatter at depthLeft == 0 begins no ray and is not counted: it stays in mS (tg, sp and
+                // ng's child bits are 0 for every lane of shadeM) as a miss, and the next SHADE step's miss
+                // branch gives it PT_SKY() of the scattered d and the multiplied att.
+                const uint64_t lastM = scM & __ballot(depthLeft == 0);
+                if (laneOf(lastM)) { best = -1; oct = 0u; }
+                // E. Ray start for the lanes that go on.
+                const uint64_t newRayM = ((shadeM & ~finM) | got) & ~lastM;
+#ifdef PT_DIAG
+                const unsigned long long tS4 = __builtin_amdgcn_s_memtime();
+#endif
+                if (laneOf(newRayM)) PT_BEGIN_RAY(false);
+#ifdef PT_DIAG
+                // (shading: steps A and B up to the tasks, and the trial loop with the slots, C and D)
+                cycSh += (tS1 - tK0) + (tS4 - tS3); cycTk += tS2 - tS1; cycNp += tS3 - tS2;
+                cycBr += __builtin_amdgcn_s_memtime() - tS4;
+#endif
+                PT_COUNT(sRays, (uint32_t)__popcll(newRayM));
+                PT_COUNT(sPaths, (uint32_t)__popcll(newSampleM));
+            } else {
+                bool done = false;   // the lane's sample is complete
+                bool shadowNow = false;   // NEE: the lane's next query is a shadow ray
+                if (shading) {
+                    float3 contrib = f3(0.0f, 0.0f, 0.0f);
+                    bool wasShadow = false;
+                    if constexpr (NEE) {
+                        if (shadowQ) {   // the shadow query is complete: its term if nothing was hit, then the parked scatter ray
+                            if (best < 0) {
+                                neeV[0 * kWave + lane] += neeV[3 * kWave + lane];
+                                neeV[1 * kWave + lane] += neeV[4 * kWave + lane];
+                                neeV[2 * kWave + lane] += neeV[5 * kWave + lane];
+                            }
+                            d = f3(neeV[6 * kWave + lane], neeV[7 * kWave + lane], neeV[8 * kWave + lane]);
+                            neeF[lane] = nf & ~1u;
+                            wasShadow = true;
+                        }
+                    }
+                    if (wasShadow) {
+                    } else if (best < 0) {
+                        contrib = PT_SKY();
+                        done = true;
+                    } else {
+                        int objI_;
+                        HitRec h = INST ? makeHitInst(ldScene(kargs()), (uint32_t)best & kPrimMask, closest, o, d, objI_)
+                                        : (WIDE ? makeHitFrom<!TRI>(kargs()->S.wshade, best & (int)kPrimMask, closest, o, d)
+                                                : makeHit(S, best, closest, o, d));
+#ifdef PT_DIAG
+                        if (!scatterInto(h, d, att, g, &nTrials)) {
+#else
+                        if (!scatterInto(h, d, att, g)) {
+#endif
+                            if constexpr (LIT) contrib = emitted(h, att);
+                            if constexpr (NEE) {   // the light was sampled at the hit this ray left
+                                // (instanced: the hit key's low gBits bits are the shading index)
+                                const int sk = INST ? best & ((1 << kargs()->S.gBits) - 1) : best & (int)kPrimMask;
+                                if ((nf & 2u) && sampledLight(kargs()->S.wshade, sk, h)) {
+                                    if constexpr (MIS && INST)
+                                        contrib = emittedWeightedAt(kargs()->lights,
+                                                                    instLightSlot(kargs()->instLightFirst, kargs()->lightSlot,
+                                                                                  (uint32_t)best & kPrimMask, kargs()->S.gBits),
+                                                                    kargs()->nLights, closest, d, neeV[9 * kWave + lane], contrib);
+                                    else if constexpr (MIS)
+                                        contrib = emittedWeighted(kargs()->lights, kargs()->lightSlot, kargs()->nLights, h.obj,
+                                                                  closest, d, neeV[9 * kWave + lane], contrib);
+                                    else contrib = f3(0.0f, 0.0f, 0.0f);
+                                }
+                            }
+                            done = true;
+                        } else {
+                            o = h.p;
+                            if (depthLeft == 0) { contrib = PT_SKY(); done = true; }
+                            else if constexpr (NEE) {
+                                nf &= ~2u;
+                                if (h.type == PT_LAMBERTIAN) {
+                                    nf |= 2u;
+                                    float3 w, term;
+                                    if constexpr (MIS) neeV[9 * kWave + lane] = scatterPdf(h.n, d);
+                                    if (lightSample<MIS>(kargs()->lights, kargs()->nLights, o, h.n, att, g, w, term)) {
+                                        neeV[3 * kWave + lane] = term.x; neeV[4 * kWave + lane] = term.y; neeV[5 * kWave + lane] = term.z;
+                                        neeV[6 * kWave + lane] = d.x; neeV[7 * kWave + lane] = d.y; neeV[8 * kWave + lane] = d.z;
+                                        d = w;
+                                        nf |= 1u;
+                                        shadowNow = true;
+                                    }
+                                }
+                                neeF[lane] = nf;
+                            }
+                        }
+                    }
+                    if (done) {
+                        if constexpr (NEE)
+                            contrib = neeTotal(f3(neeV[0 * kWave + lane], neeV[1 * kWave + lane], neeV[2 * kWave + lane]), contrib);
+                        sum = add(sum, contrib);
+                    }
+                }
+                // Every lane steps its sample count by `done` (a lane that is not shading by 0; shadeM
+                // masks its stale state): who completed a sample and who its last one comes from two
+                // integer compares, not from predicates joined over the branches above.
+                uint64_t doneM, finM;
+                if constexpr (SAMPLE) {
+                    const uint4 ts = taskState[lane];
+                    const uint32_t y1 = ts.y + (done ? 1u : 0u);
+                    taskState[lane].y = y1;
+                    doneM = shadeM & __ballot(y1 != ts.y);
+                    finM = doneM & __ballot(y1 == ts.z);
+                    if (laneOf(finM)) PT_FINISH_TASK(ts);
+                    needTaskM |= finM;
+                } else {
+                    const int s1 = sample + (done ? 1 : 0);
+                    doneM = shadeM & __ballot(s1 != sample);
+                    finM = doneM & __ballot(s1 == nSamples);
+                    sample = s1;
+                }
+                activeM &= ~finM;
+                // bounce or next sample (newSampleM) for the lanes that go on
+                uint64_t newRayM = shadeM & ~finM, newSampleM = doneM & ~finM;
+#ifdef PT_DIAG
+                const unsigned long long tS1 = __builtin_amdgcn_s_memtime();
+#endif
+                if constexpr (SAMPLE) {   // idle lanes take new tasks and start their first path
+                    uint64_t got = 0;
+                    PT_TAKE_TASKS(got);
+                    activeM |= got;
+                    newRayM |= got;
+                    newSampleM |= got;
+                }
+                // one camera-ray and one ray-start site for every lane that needs them
+#ifdef PT_DIAG
+                const unsigned long long tS2 = __builtin_amdgcn_s_memtime();
+#endif
+                if (laneOf(newSampleM)) PT_NEW_PATH();
+#ifdef PT_DIAG
+                const unsigned long long tS3 = __builtin_amdgcn_s_memtime();
+#endif
+                if (laneOf(newRayM)) PT_BEGIN_RAY(shadowNow);
+#ifdef PT_DIAG
+                const unsigned long long tS4 = __builtin_amdgcn_s_memtime();
+                cycSh += tS1 - tK0; cycTk += tS2 - tS1; cycNp += tS3 - tS2; cycBr += tS4 - tS3;
+#endif
+                PT_COUNT(sRays, (uint32_t)__popcll(newRayM));
+                PT_COUNT(sPaths, (uint32_t)__popcll(newSampleM));
             }
-            // one camera-ray and one ray-start site for every lane that needs them
 #ifdef PT_DIAG
-            const unsigned long long tS2 = __builtin_amdgcn_s_memtime();
+            // the step's trial-loop iterations: the wave repeats the trial as often as its slowest lane
+            for (int w_ = 32; w_ > 0; w_ >>= 1) nTrials = max(nTrials, (uint32_t)__shfl_xor((int)nTrials, w_));
+            sTrials += nTrials;
 #endif
-            if (laneOf(newSampleM)) PT_NEW_PATH();
-#ifdef PT_DIAG
-            const unsigned long long tS3 = __builtin_amdgcn_s_memtime();
-#endif
-            if (laneOf(newRayM)) PT_BEGIN_RAY(shadowNow);
-#ifdef PT_DIAG
-            const unsigned long long tS4 = __builtin_amdgcn_s_memtime();
-            cycSh += tS1 - tK0; cycTk += tS2 - tS1; cycNp += tS3 - tS2; cycBr += tS4 - tS3;
-#endif
-            PT_COUNT(sRays, (uint32_t)__popcll(newRayM));
-            PT_COUNT(sPaths, (uint32_t)__popcll(newSampleM));
         }
 #ifdef PT_DIAG
         {   // shader-clock cycles per step kind (the step's memory waits included)
@@ -2536,6 +2686,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
         atomicAdd(P.counters + 22, sIdleN);
         atomicAdd(P.counters + 23, (unsigned long long)sRedoMiss);
         atomicAdd(P.counters + 25, sHalf);
+        atomicAdd(P.counters + 26, sTrials);
         atomicAdd(P.counters + 27, sParkT);
 #endif
     }
@@ -2548,6 +2699,37 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWavesPer
 #undef PT_FINISH_TASK
 #undef PT_DIAG_ADD
 #undef PT_COUNT
+
+// Every render launch goes through these two macros (in scope: RenderParams P, hipStream_t st).
+// PT_KERNEL_LOG not 0: the launch site names the instantiation it takes, one line on stderr per launch
+// (host code; the template arguments are those of the launch itself, written out in full).
+inline bool kernelLogOn() {
+    const char* v = std::getenv("PT_KERNEL_LOG");
+    return v && std::atoi(v) != 0;
+}
+inline const char* tf(bool b) { return b ? "true" : "false"; }
+template <int STACK, bool SAMPLE, bool WIDE, bool INST = false, bool LIT = false, bool NEE = false, bool MIS = false,
+          bool TRI = false, bool AHEAD = false>
+inline void logLaunchWF() {
+    if (kernelLogOn())
+        std::fprintf(stderr, "[pt] kernel renderKernelWF<%d, %s, %s, %s, %s, %s, %s, %s, %s>\n", STACK, tf(SAMPLE), tf(WIDE),
+                     tf(INST), tf(LIT), tf(NEE), tf(MIS), tf(TRI), tf(AHEAD));
+}
+template <int STACK, bool SAMPLE, bool LIT = false, bool NEE = false, bool MIS = false>
+inline void logLaunchSimple() {
+    if (kernelLogOn())
+        std::fprintf(stderr, "[pt] kernel renderKernel<%d, %s, %s, %s, %s>\n", STACK, tf(SAMPLE), tf(LIT), tf(NEE), tf(MIS));
+}
+#define PT_LAUNCH_WF(grid, ...)                                                                     \
+    do {                                                                                          \
+        logLaunchWF<__VA_ARGS__>();                                                               \
+        renderKernelWF<__VA_ARGS__><<<(grid), kWave, 0, st>>>(P);                                 \
+    } while (0)
+#define PT_LAUNCH_SIMPLE(grid, ...)                                                                 \
+    do {                                                                                          \
+        logLaunchSimple<__VA_ARGS__>();                                                           \
+        renderKernel<__VA_ARGS__><<<(grid), kWave, 0, st>>>(P);                                   \
+    } while (0)
 
 #ifdef PT_TU_COMPAT
 }  // namespace
@@ -2562,10 +2744,10 @@ namespace pt {
 template <int S, bool TRI>
 static void launchCompatWideTri(const RenderParams& P, hipStream_t st) {
     const int grid = P.compatGrid;
-    if (P.nLights > 0 && P.mis) renderKernelWF<S, false, true, false, true, true, true, TRI><<<grid, kWave, 0, st>>>(P);
-    else if (P.nLights > 0) renderKernelWF<S, false, true, false, true, true, false, TRI><<<grid, kWave, 0, st>>>(P);
-    else if (P.lit) renderKernelWF<S, false, true, false, true, false, false, TRI><<<grid, kWave, 0, st>>>(P);
-    else renderKernelWF<S, false, true, false, false, false, false, TRI><<<grid, kWave, 0, st>>>(P);
+    if (P.nLights > 0 && P.mis) PT_LAUNCH_WF(grid, S, false, true, false, true, true, true, TRI);
+    else if (P.nLights > 0) PT_LAUNCH_WF(grid, S, false, true, false, true, true, false, TRI);
+    else if (P.lit) PT_LAUNCH_WF(grid, S, false, true, false, true, false, false, TRI);
+    else PT_LAUNCH_WF(grid, S, false, true, false, false, false, false, TRI);
 }
 int launchCompatWide(int stack, const void* params, hipStream_t st) {
     const RenderParams& P = *static_cast<const RenderParams*>(params);
@@ -3785,6 +3967,7 @@ struct pt_scene {
     float sceneCE[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // tight scene box: centre, largest extent (DevScene)
     float skyH[3] = {1.0f, 1.0f, 1.0f}, skyZ[3] = {0.5f, 0.7f, 1.0f};   // pt_scene_set_sky (default: main.cu:34-36)
     bool hasEmissive = false;               // any PT_EMISSIVE material
+    bool lambertOnly = true;                // no PT_METAL or PT_DIELECTRIC material: only the unit-sphere loop draws on a path
     // PT_RENDER_NEE: the sampled lights (emissive triangles) of the last build, listed on the device
     // (lightFlagKernel, a scan, lightListKernel); the buffers are kept between builds
     std::vector<uint8_t> matEmissive;       // per material: its type is PT_EMISSIVE
@@ -4188,17 +4371,28 @@ int setDevice(int dev) {
     return PT_OK;
 }
 
+// The AHEAD instantiations that exist: triangle-only kernels at the stacks where a wave's 768 more
+// bytes of LDS leave five waves per SIMD (the 24-entry stack's 20 waves would need 165 KB of 160).
+template <int S, bool TRI>
+constexpr bool kAheadFor = TRI && S <= 16;
+inline bool aheadStack(int stack) { return stack == 8 || stack == 16; }
 // Sample mode on a flat scene.  TRI = P.tri: the triangle-only instantiations.
 template <int S, bool LIT, bool TRI>
 void launchSampleWideFlat(const RenderParams& P, hipStream_t st) {
     if constexpr (LIT) {   // (NEE launches are LIT: a sampled light is an emissive material)
         if (P.nLights > 0) {
-            if (P.mis) renderKernelWF<S, true, true, false, true, true, true, TRI><<<P.nwaves, kWave, 0, st>>>(P);
-            else renderKernelWF<S, true, true, false, true, true, false, TRI><<<P.nwaves, kWave, 0, st>>>(P);
+            if (P.mis) PT_LAUNCH_WF(P.nwaves, S, true, true, false, true, true, true, TRI);
+            else PT_LAUNCH_WF(P.nwaves, S, true, true, false, true, true, false, TRI);
             return;
         }
     }
-    renderKernelWF<S, true, true, false, LIT, false, false, TRI><<<P.nwaves, kWave, 0, st>>>(P);
+    if constexpr (kAheadFor<S, TRI>) {   // (P.ahead: set for these instantiations only, pt_render_ex)
+        if (P.ahead) {
+            PT_LAUNCH_WF(P.nwaves, S, true, true, false, LIT, false, false, TRI, true);
+            return;
+        }
+    }
+    PT_LAUNCH_WF(P.nwaves, S, true, true, false, LIT, false, false, TRI);
 }
 // LIT = P.lit (dispatchRender): the kernels with the emissive exit and the scene's own sky
 template <int S, bool LIT>
@@ -4206,15 +4400,15 @@ void launchRenderWide(const RenderParams& P, hipStream_t st) {
     if (P.S.winst) {   // an instanced scene's two-level tree
         if constexpr (LIT) {   // (built with PT_BVH_LIGHTS: the NEE / MIS kernels, as below)
             if (P.nLights > 0) {
-                if (P.pixAcc && P.mis) renderKernelWF<S, true, true, true, true, true, true><<<P.nwaves, kWave, 0, st>>>(P);
-                else if (P.pixAcc) renderKernelWF<S, true, true, true, true, true><<<P.nwaves, kWave, 0, st>>>(P);
-                else if (P.mis) renderKernelWF<S, false, true, true, true, true, true><<<P.compatGrid, kWave, 0, st>>>(P);
-                else renderKernelWF<S, false, true, true, true, true><<<P.compatGrid, kWave, 0, st>>>(P);
+                if (P.pixAcc && P.mis) PT_LAUNCH_WF(P.nwaves, S, true, true, true, true, true, true);
+                else if (P.pixAcc) PT_LAUNCH_WF(P.nwaves, S, true, true, true, true, true);
+                else if (P.mis) PT_LAUNCH_WF(P.compatGrid, S, false, true, true, true, true, true);
+                else PT_LAUNCH_WF(P.compatGrid, S, false, true, true, true, true);
                 return;
             }
         }
-        if (P.pixAcc) renderKernelWF<S, true, true, true, LIT><<<P.nwaves, kWave, 0, st>>>(P);
-        else renderKernelWF<S, false, true, true, LIT><<<P.compatGrid, kWave, 0, st>>>(P);
+        if (P.pixAcc) PT_LAUNCH_WF(P.nwaves, S, true, true, true, LIT);
+        else PT_LAUNCH_WF(P.compatGrid, S, false, true, true, LIT);
         return;
     }
     if (P.pixAcc) {
@@ -4226,20 +4420,20 @@ void launchRenderWide(const RenderParams& P, hipStream_t st) {
 template <int S, bool LIT>
 void launchRender(const RenderParams& P, hipStream_t st) {
     if (P.kernel == PT_KERNEL_WAVEFRONT && P.pixAcc)
-        renderKernelWF<S, true, false, false, LIT><<<P.nwaves, kWave, 0, st>>>(P);
+        PT_LAUNCH_WF(P.nwaves, S, true, false, false, LIT);
     else if (P.kernel == PT_KERNEL_WAVEFRONT)
-        renderKernelWF<S, false, false, false, LIT><<<P.compatGrid, kWave, 0, st>>>(P);
-    else if (LIT && P.nLights > 0 && P.mis && P.pixAcc) renderKernel<S, true, LIT, LIT, LIT><<<P.ntiles, kWave, 0, st>>>(P);
-    else if (LIT && P.nLights > 0 && P.mis) renderKernel<S, false, LIT, LIT, LIT><<<P.ntiles, kWave, 0, st>>>(P);
-    else if (LIT && P.nLights > 0 && P.pixAcc) renderKernel<S, true, LIT, LIT><<<P.ntiles, kWave, 0, st>>>(P);
-    else if (LIT && P.nLights > 0) renderKernel<S, false, LIT, LIT><<<P.ntiles, kWave, 0, st>>>(P);
-    else if (P.pixAcc) renderKernel<S, true, LIT><<<P.ntiles, kWave, 0, st>>>(P);
-    else renderKernel<S, false, LIT><<<P.ntiles, kWave, 0, st>>>(P);
+        PT_LAUNCH_WF(P.compatGrid, S, false, false, false, LIT);
+    else if (LIT && P.nLights > 0 && P.mis && P.pixAcc) PT_LAUNCH_SIMPLE(P.ntiles, S, true, LIT, LIT, LIT);
+    else if (LIT && P.nLights > 0 && P.mis) PT_LAUNCH_SIMPLE(P.ntiles, S, false, LIT, LIT, LIT);
+    else if (LIT && P.nLights > 0 && P.pixAcc) PT_LAUNCH_SIMPLE(P.ntiles, S, true, LIT, LIT);
+    else if (LIT && P.nLights > 0) PT_LAUNCH_SIMPLE(P.ntiles, S, false, LIT, LIT);
+    else if (P.pixAcc) PT_LAUNCH_SIMPLE(P.ntiles, S, true, LIT);
+    else PT_LAUNCH_SIMPLE(P.ntiles, S, false, LIT);
 }
-template <int S, bool WIDE, bool INST = false, bool SAMPLE = true, bool TRI = false>
+template <int S, bool WIDE, bool INST = false, bool SAMPLE = true, bool TRI = false, bool AHEAD = false>
 int wavesPerCU(int& n) {
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &n, reinterpret_cast<const void*>(&renderKernelWF<S, SAMPLE, WIDE, INST, false, false, false, TRI>), kWave, 0));
+        &n, reinterpret_cast<const void*>(&renderKernelWF<S, SAMPLE, WIDE, INST, false, false, false, TRI, AHEAD>), kWave, 0));
     return PT_OK;
 }
 // A run-time stack size as a compile-time constant: f(std::integral_constant<int, N>) for the N
@@ -4259,8 +4453,14 @@ bool withBinStack(int stack, F f) { return withStack<16, 24, 32, 48, 64, 80>(sta
 // the same LDS and waves-per-SIMD attribute, so the same occupancy (DESIGN.md's resource table).
 // The compat wide kernels live in pt_compat.hip's
 // translation unit.  tri: the launch runs a TRI instantiation (RenderParams::tri), which is asked.
-int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, bool nee, bool mis, bool tri) {
+int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, bool nee, bool mis, bool tri, bool ahead) {
     const bool wide = kernel == PT_KERNEL_WIDE;
+    if (ahead) {   // (wide, sample, flat, tri, no NEE: the AHEAD kernels hold the slots' LDS, so they are asked themselves)
+        int rc = PT_OK;
+        const bool ok = withStack<8, 16>(stack, [&](auto N) { rc = wavesPerCU<decltype(N)::value, true, false, true, true, true>(n); });
+        if (!ok) return fail(PT_ERR_STATE, "unsupported wide BVH depth");
+        return rc;
+    }
     if (wide && sample && nee) {   // the NEE and MIS kernels hold more LDS per wave: asked of themselves
         int rc = PT_OK;
         const bool ok = withWideStack(stack, [&](auto N) {
@@ -4434,6 +4634,9 @@ void printIterStats(const unsigned long long* c, bool wide) {
         std::fprintf(stderr, "[pt] SHADE cycles/iteration: shading %.0f tasks %.0f new-path %.0f ray-start %.0f\n",
                      (double)c[16] / std::max(1ull, c[10]), (double)c[17] / std::max(1ull, c[10]),
                      (double)c[18] / std::max(1ull, c[10]), (double)c[19] / std::max(1ull, c[10]));
+    if (c[26] > 0)
+        std::fprintf(stderr, "[pt] SHADE unit-sphere trial-loop iterations %llu (%.2f per SHADE step)\n", c[26],
+                     (double)c[26] / std::max(1ull, c[10]));
 }
 
 // The film's last render -> pt_stats: waits for its counters (copied to pinned memory in stream
@@ -4491,6 +4694,8 @@ int pt_scene_create(int device, const pt_object* objs, int64_t n, const pt_mater
     s->nobj = n;
     s->nmat = nmat;
     s->hasEmissive = emissive;
+    for (int64_t i = 0; i < nmat; i++)
+        if (mats[i].type == PT_METAL || mats[i].type == PT_DIELECTRIC) s->lambertOnly = false;
     s->matEmissive.resize((size_t)nmat);
     for (int64_t i = 0; i < nmat; i++) s->matEmissive[(size_t)i] = mats[i].type == PT_EMISSIVE ? 1 : 0;
     s->objs.assign(objs, objs + n);
@@ -5419,6 +5624,11 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     }
     const bool lpt = !(opts && (opts->flags & PT_RENDER_IDENTITY_ORDER));
     const bool sample = rng == PT_RNG_SAMPLE && np > 0 && P.ntiles > 0;
+    // The AHEAD kernels: a triangle-only flat scene in sample mode on the wide kernel, no material that
+    // draws outside the unit-sphere loop, a pinhole camera, no light sampling, a stack they are built for
+    // (PT_SHADE_AHEAD=0: today's kernels in the same library, for tests and A/B runs).
+    P.ahead = sample && P.tri && s->lambertOnly && cam->lens_radius == 0.0f && !nee && aheadStack(stack) &&
+                      envCount("PT_SHADE_AHEAD", 1) != 0 ? 1 : 0;
     if (!f->cus) {
         if (hipDeviceGetAttribute(&f->cus, hipDeviceAttributeMultiprocessorCount, f->device) != hipSuccess)
             f->cus = 256;
@@ -5428,16 +5638,16 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
     // occupancy per CU, which the LDS stack caps on deep trees.  Queried once per (device, kernel
     // instantiation) and process.
     auto perCUFor = [&](int& perCU) -> int {
-        static std::atomic<int> cached[16][2][2][2][3][3][2];   // [device][sample][instanced][wide][stack 8, 16, 24][blind, nee, mis][tri]
+        static std::atomic<int> cached[16][2][2][2][3][3][2][2];   // [device][sample][instanced][wide][stack 8, 16, 24][blind, nee, mis][tri][ahead]
         const bool small = stack <= 24 && stack % 8 == 0 && f->device >= 0 && f->device < 16;
         std::atomic<int>* c = small ? &cached[f->device][sample ? 1 : 0][s->instanced ? 1 : 0]
-                                             [kernel == PT_KERNEL_WIDE ? 1 : 0][stack / 8 - 1][mis ? 2 : nee ? 1 : 0][P.tri] : nullptr;
+                                             [kernel == PT_KERNEL_WIDE ? 1 : 0][stack / 8 - 1][mis ? 2 : nee ? 1 : 0][P.tri][P.ahead] : nullptr;
         const int known = c ? c->load(std::memory_order_relaxed) : 0;
         if (known > 0) {
             perCU = known;
             return PT_OK;
         }
-        if (int r = persistentWavesPerCU(stack, kernel, perCU, s->instanced, sample, nee, mis, P.tri != 0)) return r;
+        if (int r = persistentWavesPerCU(stack, kernel, perCU, s->instanced, sample, nee, mis, P.tri != 0, P.ahead != 0)) return r;
         if (c) c->store(perCU, std::memory_order_relaxed);
         return PT_OK;
     };
