@@ -606,6 +606,65 @@ int pt_render_aov(pt_scene* scene, pt_film* film, const pt_camera* cam, pt_aov* 
 typedef struct { int32_t iterations; float sigma_color, sigma_albedo, sigma_plane; int32_t reserved[4]; } pt_denoise_opts;
 int pt_film_denoise(pt_film* film, const float* rgb, const pt_aov* aov, float* out, int on_device, void* stream,
                     const pt_denoise_opts* opts);
+/* Temporal reprojection of the film's frame history, the temporal half of SVGF-style denoisers: the
+ * colour accumulated over the earlier calls is carried into the new camera through the guides' world
+ * positions, tested against the guides and blended with the new frame, so that samples survive a
+ * pt_camera_move (PT_RENDER_ACCUMULATE keeps them only while the camera stands still).
+ * rgb and out are W x H x 3 floats in film order, aov W x H records of the same frame, out_len NULL or W x H
+ * floats (each pixel's history length); cam is the camera rgb and aov were rendered with: the film keeps it
+ * by value as the next call's previous camera.  Pointers and stream as pt_film_denoise: on_device = 0: host
+ * pointers, copied in and out, the call is synchronous; otherwise device pointers, one kernel launch is
+ * enqueued on `stream` and the call returns without waiting (aov 16-byte aligned, as pt_render_aov's
+ * device output: its rows are read as 16-byte words).  out may equal rgb (a pixel reads rgb and aov
+ * only at itself).  Only a film that owns the whole frame (n_parts == 1): a stripe would need halos.  Calls on
+ * one film use one stream, or are ordered by the caller.
+ * The film owns two history images that take turns (taps read neighbours of the old one, so it is not updated
+ * in place; they are swapped when the call is enqueued), 48 B per pixel each -- three 16-byte rows {acc.rgb,
+ * len}, {n, mat}, {p, hit flag} -- allocated at first use and freed by pt_film_destroy, the previous camera and
+ * a "has history" flag.  They share nothing with pt_film_denoise's scratch images: a temporal call followed by
+ * a denoise call on one stream compose.  The film's streams, accumulators, pt_film_stats and
+ * pt_film_accumulated are not touched, and the history is independent of pt_film_clear and pt_film_reset.
+ * pt_film_temporal_reset clears the flag and enqueues nothing: the next call starts a new history.
+ * The history advances when the launch is enqueued; with host pointers, when the results have been copied
+ * back: a call that returns an error leaves it as it was.
+ * opts: NULL means {32.0f, 0.02f, 0.9f, 0}; max_history finite and >= 1, sigma_plane finite and > 0,
+ * normal_cos finite and in [-1, 1]; flag bits other than PT_TEMPORAL_LINEAR are ignored.  PT_ERR_INVALID --
+ * nothing enqueued; out, out_len and the history untouched -- for anything else, for a NULL film, rgb, aov,
+ * cam or out, and for a partitioned film.
+ * The rule.  Every operation is one rounded fp32 operation in the written order (no contraction, IEEE
+ * division, correctly rounded sqrtf, denormals kept); dot and cross as defined at PT_RENDER_NEE.  Every test
+ * reads "kept only when the comparison is true": a NaN rejects.
+ * Pixel (x, y) with record P and colour c:  cur = c * c per channel (PT_TEMPORAL_LINEAR: cur = c).
+ * have = false when the film has no history (the first call, the first after a reset, or a history of
+ * another size: a film's size is fixed, so that cannot arise through this ABI) or P.obj < 0 (a
+ * miss pixel never has history: the sky carries no position).  Otherwise, with the previous camera {o =
+ * origin, ll = lower_left, hor = horizontal, ver = vertical}:
+ *   a = ll - o;  w = P.p - o;  cvw = cross(ver, w);  cwh = cross(w, hor);  chv = cross(hor, ver);
+ *   den = dot(hor, cvw);  u = (-dot(a, cvw)) / den;  v = (-dot(a, cwh)) / den;  k = dot(a, chv) / den
+ *   fx = u * (float)W - 0.5f;  fy = v * (float)H - 0.5f
+ *   kept only when k > 0 && fx > -1 && fx < W && fy > -1 && fy < H   (the lens is ignored, as in pt_render_aov)
+ *   x0 = floorf(fx);  y0 = floorf(fy);  tx = fx - x0;  ty = fy - y0
+ *   ah = 0, al = 0, ws = 0; taps j = 0, 1 outer, i = 0, 1 inner, q = (x0 + i, y0 + j); a tap outside the frame
+ *   is skipped.  wq = (i ? tx : 1 - tx) * (j ? ty : 1 - ty).  With Q the history pixel at q the tap is kept only
+ *   when Q was a hit, Q.mat == P.mat, dot(P.n, Q.n) >= normal_cos,
+ *   fabsf(dot(P.n, Q.p - P.p)) <= sigma_plane * P.depth,
+ *   (fabsf(Q.acc.r) + fabsf(Q.acc.g)) + fabsf(Q.acc.b) < INFINITY, and wq > 0.
+ *   a kept tap:  ah.ch = ah.ch + wq * Q.acc.ch per channel;  al = al + wq * Q.len;  ws = ws + wq
+ *   have = ws > 0;  then h.ch = ah.ch / ws,  nh = al / ws
+ * Blend:  len = have ? fminf(nh + 1, max_history) : 1;  alpha = 1 / len;
+ *   acc.ch = have ? h.ch + (cur.ch - h.ch) * alpha : cur.ch;  out.ch = sqrtf(acc.ch) (PT_TEMPORAL_LINEAR:
+ *   out.ch = acc.ch);  out_len = len.  The new history pixel is {acc, len} with P's n, mat, p and hit flag.
+ * Consequences: the history is a mean in linear radiance (pt_render's output is its square root; averaging
+ * sqrt(mean) values would darken the image).  Scenes are assumed static: there are no motion vectors, so
+ * after pt_scene_update_objects, pt_scene_update_instances or pt_scene_set_sky the caller resets.  A
+ * non-finite history colour is never carried forward.  max_history == 1 turns the filter off, to rounding:
+ * len is 1 everywhere, and a pixel with history still evaluates h + (cur - h) * 1.  The guides are
+ * those of the first hit, so pt_film_denoise's limitation on mirrors and glass applies unchanged. */
+#define PT_TEMPORAL_LINEAR 1
+typedef struct { float max_history, sigma_plane, normal_cos; int32_t flags; int32_t reserved[4]; } pt_temporal_opts;
+int pt_film_temporal(pt_film* film, const float* rgb, const pt_aov* aov, const pt_camera* cam,
+                     float* out, float* out_len, int on_device, void* stream, const pt_temporal_opts* opts);
+int pt_film_temporal_reset(pt_film* film);
 /* Re-initialise the film's streams to their initRandom state (asynchronous on `stream`). */
 int pt_film_reset(pt_film* film, void* stream);
 /* Progressive rendering: zero the film's accumulated sums (asynchronous on `stream`); the number

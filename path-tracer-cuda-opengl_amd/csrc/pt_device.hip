@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../host/pt_denoise_dev.hpp"
+#include "../host/pt_temporal_dev.hpp"
 #include "../host/pt_error.hpp"
 #include "../host/pt_host.hpp"
 #include "../host/pt_inst_dev.hpp"
@@ -4037,6 +4038,14 @@ struct pt_film {
     DevBuf aovStaging;            // pt_render_aov: device copy of a host output
     DevBuf dnA, dnB;              // pt_film_denoise: the passes' two scratch images, allocated at first use and kept
     DevBuf dnRgb, dnAov;          // pt_film_denoise with host pointers: device copies of the image (in, then out) and the guides
+    // pt_film_temporal: the two history images (48 B per pixel; a call gathers from tpHist[tpCur] and writes
+    // the other), allocated at first use and kept; the camera of the frame in tpHist[tpCur]; whether there
+    // is one (cleared by pt_film_temporal_reset); with host pointers, device copies of rgb / out, aov, out_len
+    DevBuf tpHist[2];
+    DevBuf tpRgb, tpAov, tpLen;
+    int tpCur = 0;
+    bool tpHave = false;
+    pt_camera tpCam = {};
     int64_t accumSamples = 0;     // samples per pixel in `accum`
     int cus = 0;                  // compute units of the device (persistent grid size)
     // The last render's work counters (rays, visits, tests, paths, error word), filled by its
@@ -5439,6 +5448,71 @@ int pt_film_denoise(pt_film* f, const float* rgb, const pt_aov* aov, float* out,
         HIP_TRY(hipStreamSynchronize(st));
     }
     guard.ok = true;
+    return PT_OK;
+}
+
+int pt_film_temporal(pt_film* f, const float* rgb, const pt_aov* aov, const pt_camera* cam, float* out, float* out_len,
+                     int on_dev, void* stream, const pt_temporal_opts* opts) {
+    static_assert(sizeof(pt_temporal_opts) == 32, "pt_temporal_opts: eight 4-byte fields");
+    const pt_temporal_opts dflt = {32.0f, 0.02f, 0.9f, 0, {0, 0, 0, 0}};
+    const pt_temporal_opts o = opts ? *opts : dflt;
+    if (!std::isfinite(o.max_history) || !(o.max_history >= 1.0f))
+        return fail(PT_ERR_INVALID, "pt_film_temporal: max_history must be finite and >= 1");
+    if (!std::isfinite(o.sigma_plane) || !(o.sigma_plane > 0.0f))
+        return fail(PT_ERR_INVALID, "pt_film_temporal: sigma_plane must be finite and > 0");
+    if (!(o.normal_cos >= -1.0f && o.normal_cos <= 1.0f))
+        return fail(PT_ERR_INVALID, "pt_film_temporal: normal_cos must lie in [-1, 1]");
+    if (!f || !rgb || !aov || !cam || !out) return fail(PT_ERR_INVALID, "pt_film_temporal: null argument");
+    if (f->nparts != 1) return fail(PT_ERR_INVALID, "pt_film_temporal: the film must own the whole frame (n_parts == 1)");
+    int rc = setDevice(f->device);
+    if (rc) return rc;
+    hipStream_t st = on_dev ? (hipStream_t)stream : 0;
+    const size_t np = (size_t)f->npix;
+    for (DevBuf& h : f->tpHist)
+        if ((rc = devReserve(h, np * pt::kHistoryBytes))) return rc;
+    const float* src = rgb;
+    float *dst = out, *dlen = out_len;
+    if (!on_dev) {
+        if ((rc = devReserve(f->tpRgb, np * 12)) || (rc = devReserve(f->tpAov, np * sizeof(pt_aov)))) return rc;
+        if (out_len && (rc = devReserve(f->tpLen, np * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(f->tpRgb.p, rgb, np * 12, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(f->tpAov.p, aov, np * sizeof(pt_aov), hipMemcpyHostToDevice, st));
+        src = dst = f->tpRgb.as<float>();
+        aov = f->tpAov.as<pt_aov>();
+        dlen = out_len ? f->tpLen.as<float>() : nullptr;
+    }
+    StreamWait guard(st);
+    pt::TemporalParams K;
+    for (int a = 0; a < 3; a++) {
+        K.o[a] = f->tpCam.origin[a];
+        K.ll[a] = f->tpCam.lower_left[a];
+        K.hor[a] = f->tpCam.horizontal[a];
+        K.ver[a] = f->tpCam.vertical[a];
+    }
+    K.maxHistory = o.max_history;
+    K.sigmaPlane = o.sigma_plane;
+    K.normalCos = o.normal_cos;
+    K.width = f->width;
+    K.height = f->height;
+    K.haveHistory = f->tpHave ? 1 : 0;
+    K.linear = (o.flags & PT_TEMPORAL_LINEAR) ? 1 : 0;
+    HIP_TRY(pt::temporalPass(src, aov, f->tpHist[f->tpCur].p, f->tpHist[f->tpCur ^ 1].p, dst, dlen, K, st));
+    if (!on_dev) {   // synchronous: the history advances only when the caller has its result
+        HIP_TRY(hipMemcpyAsync(out, f->tpRgb.p, np * 12, hipMemcpyDeviceToHost, st));
+        if (out_len) HIP_TRY(hipMemcpyAsync(out_len, f->tpLen.p, np * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    // The images take turns at enqueue time: the next call on this stream gathers from what this one writes.
+    f->tpCur ^= 1;
+    f->tpHave = true;
+    f->tpCam = *cam;
+    guard.ok = true;
+    return PT_OK;
+}
+
+int pt_film_temporal_reset(pt_film* f) {
+    if (!f) return fail(PT_ERR_INVALID, "pt_film_temporal_reset: null film");
+    f->tpHave = false;
     return PT_OK;
 }
 

@@ -66,6 +66,12 @@ class DenoiseOpts(C.Structure):
                 ("sigma_plane", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
+class TemporalOpts(C.Structure):
+    _fields_ = [("max_history", C.c_float), ("sigma_plane", C.c_float), ("normal_cos", C.c_float),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+TEMPORAL_LINEAR = 1   # PT_TEMPORAL_LINEAR: rgb and out are linear radiance (no square / square root)
 RNG_COMPAT, RNG_SAMPLE = 0, 1
 IDENTITY_ORDER, ACCUMULATE = 1, 2
 NEE = 4   # PT_RENDER_NEE: next-event estimation (direct sampling of the emissive triangles)
@@ -112,6 +118,7 @@ EXPORTS = [
     "pt_scene_create_instanced", "pt_trace_occluded", "pt_trace_occluded_device",
     "pt_scene_update_instances", "pt_scene_set_sky", "pt_preset_sky", "pt_scene_light_count",
     "pt_scene_download_lights", "pt_scene_download_wide", "pt_render_aov", "pt_film_denoise",
+    "pt_film_temporal", "pt_film_temporal_reset",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -178,6 +185,8 @@ _sig = {
                                C.POINTER(Stats)]),
     "pt_render_aov": (C.c_int, [_P, _P, C.POINTER(Camera), _P, C.c_int, _P, C.POINTER(Stats)]),
     "pt_film_denoise": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.POINTER(DenoiseOpts)]),
+    "pt_film_temporal": (C.c_int, [_P, _P, _P, C.POINTER(Camera), _P, _P, C.c_int, _P, C.POINTER(TemporalOpts)]),
+    "pt_film_temporal_reset": (C.c_int, [_P]),
     "pt_film_reset": (C.c_int, [_P, _P]),
     "pt_film_clear": (C.c_int, [_P, _P]),
     "pt_film_accumulated": (C.c_int, [_P, C.POINTER(C.c_int64)]),
@@ -550,6 +559,11 @@ class Film:
         """Progressive rendering: restart the accumulation (e.g. after the camera moved)."""
         _check(lib.pt_film_clear(self.h, C.c_void_p(int(stream) if stream else 0)), "pt_film_clear")
 
+    def temporal_reset(self) -> None:
+        """pt_film_temporal_reset: forget the frame history (after a scene edit or a sky change); the
+        next temporal() call starts a new one.  Nothing is enqueued."""
+        _check(lib.pt_film_temporal_reset(self.h), "pt_film_temporal_reset")
+
     def stats(self) -> "Stats":
         """pt_film_stats: counters and kernel time of the last render (waits for it)."""
         st = Stats()
@@ -655,4 +669,30 @@ def denoise(film: Film, rgb, aov, out=None, stream=None, iterations: int = 5, si
         return res
     _check(lib.pt_film_denoise(film.h, C.c_void_p(int(rgb)), C.c_void_p(int(aov)), C.c_void_p(int(out if out is not None else rgb)),
                                1, C.c_void_p(int(stream) if stream else 0), C.byref(opts)), "pt_film_denoise")
+    return None
+
+
+def temporal(film: Film, rgb, aov, camera: Camera, out=None, out_len=None, stream=None, max_history: float = 32.0,
+             sigma_plane: float = 0.02, normal_cos: float = 0.9, linear: bool = False):
+    """pt_film_temporal: carry the film's accumulated frame history into `camera` (the camera rgb and aov
+    were rendered with), test it against the guides and blend (pt.h states every operation), for a film
+    that owns its whole frame.  rgb / aov / out / out_len are numpy arrays (float32 n_pixels x 3, AOV_DTYPE
+    n_pixels, float32 n_pixels; the call is synchronous and returns (out, len)) or integer device pointers
+    (the launch is enqueued on `stream` and None is returned; out defaults to rgb, out_len may stay None)."""
+    opts = TemporalOpts(max_history, sigma_plane, normal_cos, TEMPORAL_LINEAR if linear else 0)
+    if isinstance(rgb, np.ndarray):
+        assert isinstance(aov, np.ndarray) and (out is None or isinstance(out, np.ndarray))
+        assert out_len is None or isinstance(out_len, np.ndarray)
+        assert rgb.dtype == np.float32 and rgb.flags["C_CONTIGUOUS"] and rgb.size == film.n_pixels * 3
+        assert aov.dtype == AOV_DTYPE and aov.flags["C_CONTIGUOUS"] and aov.size == film.n_pixels
+        res = np.zeros((film.n_pixels, 3), np.float32) if out is None else out
+        length = np.zeros(film.n_pixels, np.float32) if out_len is None else out_len
+        assert res.dtype == np.float32 and res.flags["C_CONTIGUOUS"] and res.size == film.n_pixels * 3
+        assert length.dtype == np.float32 and length.flags["C_CONTIGUOUS"] and length.size == film.n_pixels
+        _check(lib.pt_film_temporal(film.h, _ptr(rgb), _ptr(aov), C.byref(camera), _ptr(res), _ptr(length), 0, None,
+                                    C.byref(opts)), "pt_film_temporal")
+        return res, length
+    _check(lib.pt_film_temporal(film.h, C.c_void_p(int(rgb)), C.c_void_p(int(aov)), C.byref(camera),
+                                C.c_void_p(int(out if out is not None else rgb)), C.c_void_p(int(out_len) if out_len else 0),
+                                1, C.c_void_p(int(stream) if stream else 0), C.byref(opts)), "pt_film_temporal")
     return None
