@@ -36,12 +36,20 @@
 #include "../host/pt_host.hpp"
 #include "../host/pt_inst_dev.hpp"
 #include "../host/pt_instancing.hpp"
+#include "../host/pt_render_plan.hpp"
 #include "../host/pt_wide8.hpp"
 #include "../host/pt_wide_dev.hpp"
 #include "pt.h"
 #include "pt_math.hpp"
 
 using pt::fail;
+// The launch plan's knobs and helpers that this file reads as well (host/pt_render_plan.hpp)
+using pt::critFor;
+using pt::envCount;
+using pt::envInt;
+using pt::kInstFarExt;
+using pt::kTaskPool;
+using pt::stackFor;
 
 #include "pt_prims.hpp"   // radixSortPairs (pt_sort.hip)
 
@@ -724,13 +732,7 @@ __device__ __forceinline__ bool wideFar(float cx, float cy, float cz, float ext,
     return !(m <= kWideFarExt * ext);   // (NaN: far)
 }
 __device__ __forceinline__ bool wideFar(const DevScene& S, float3 o) { return wideFar(S.cx, S.cy, S.cz, S.ext, o); }
-// Instanced scenes draw the line at 2 world extents: their mesh trees are quantised for origins
-// within that reach (buildInstanced), 4x finer planes than 8 extents would allow (c5i 503 -> 498
-// ms); farther origins start at their entry into the world (instEntry).
-#ifndef PT_INST_FAR_EXT
-#define PT_INST_FAR_EXT 2.0f
-#endif
-constexpr float kInstFarExt = PT_INST_FAR_EXT;
+// Instanced scenes draw the line at kInstFarExt = 2 world extents (PT_INST_FAR_EXT, host/pt_render_plan.hpp)
 static_assert(kInstFarExt >= 1.0f, "instEntry's cube (centre +- ext) must lie inside the quantised reach");
 __device__ __forceinline__ bool instFar(const DevScene& S, float3 o) {
     const float m = fmaxf(fmaxf(fabsf(o.x - S.cx), fabsf(o.y - S.cy)), fabsf(o.z - S.cz));
@@ -1255,20 +1257,7 @@ __device__ __forceinline__ float3 skyOf(const RenderParams& P, float3 d, float3 
     else return sky(d, att);
 }
 
-// compat critical pixels: how many (PT_CRIT_PIXELS) and how many per wave (PT_CRIT_LANES)
-#ifndef PT_CRIT_PIXELS
-#define PT_CRIT_PIXELS 256
-#endif
-#ifndef PT_CRIT_LANES
-#define PT_CRIT_LANES 4
-#endif
-constexpr int kCritPixels = PT_CRIT_PIXELS;
-constexpr int kCritLanes = PT_CRIT_LANES;
-// which compat kernels have critical-pixel waves: the flattened wide tree on shallow trees (stack 8:
-// the 4-waves/SIMD compat kernels, whose 128-VGPR budget holds the per-lane loop without spills)
-__host__ __device__ constexpr bool critFor(bool sample, bool wide, bool inst, int stack) {
-    return !sample && wide && !inst && stack <= 8;
-}
+// (compat critical pixels -- PT_CRIT_PIXELS, PT_CRIT_LANES, critFor: host/pt_render_plan.hpp)
 // (blockFixed, blockFixedSmall, fixedToFloat: pt_math.hpp)
 // One finished (pixel, block) task: its sum added to the pixel's accumulator, and -- on frames
 // that measure tile costs (`cost`: the input of the next launches' longest-first order) -- its ray
@@ -1508,10 +1497,8 @@ constexpr int kLeafQ = PT_LEAF_QUEUE;
 #ifndef PT_LEAF_QUEUE_SAMPLE
 #define PT_LEAF_QUEUE_SAMPLE 2   // sample mode, binary tree, STACK <= 32; compat prefers 4 (C3 1774 vs 1959 ms)
 #endif
-#ifndef PT_TASK_POOL
-#define PT_TASK_POOL 64
-#endif
-constexpr int kTaskPool = PT_TASK_POOL;   // sample mode: tasks a wave reserves per atomic
+// (PT_TASK_POOL, kTaskPool -- sample mode: tasks a wave reserves per atomic -- and PT_LDS_STACK --
+// traversal stack entries per lane kept in LDS: host/pt_render_plan.hpp)
 // Occupancy target of the wavefront kernel (waves per SIMD; 6 = at most 80 VGPRs).  The LDS
 // stack (STACK x 256 B per wave, 160 KB per CU) allows 6 / 5 / 4 / 3 / 2 waves per SIMD at
 // STACK 24 / 32 / 48 / 64 / 80, so deeper trees keep a larger register budget.  Compat tile
@@ -1519,9 +1506,6 @@ constexpr int kTaskPool = PT_TASK_POOL;   // sample mode: tasks a wave reserves 
 // 4 waves 910 ms, 5 waves 815 ms, 6 waves 754 ms.
 #ifndef PT_WAVES_PER_EU
 #define PT_WAVES_PER_EU 6
-#endif
-#ifndef PT_LDS_STACK
-#define PT_LDS_STACK 32   // sample mode: traversal stack entries per lane kept in LDS
 #endif
 template <int STACK, bool SAMPLE, bool WIDE>
 constexpr int kLdsStack = (!WIDE && STACK > PT_LDS_STACK) ? PT_LDS_STACK : STACK;
@@ -3869,21 +3853,17 @@ int devReserve(DevBuf& b, size_t bytes) {
     return devAlloc(b, bytes);
 }
 
-int envInt(const char* name, int dflt) {
-    const char* v = std::getenv(name);
-    if (!v || !*v) return dflt;
-    int x = std::atoi(v);
-    if (x < 1) return dflt;   // "0": the default
-    return x > 64 ? 64 : x;
-}
-// A count knob: any value >= 0 (0 is zero, not the default); unset or unparsable: the default.
-int envCount(const char* name, int dflt) {
-    const char* v = std::getenv(name);
-    if (!v || !*v) return dflt;
-    char* end = nullptr;
-    const long x = std::strtol(v, &end, 10);
-    if (end == v || x < 0) return dflt;
-    return (int)std::min<long>(x, 1L << 30);
+// (envInt, envCount: host/pt_render_plan.hpp)
+
+// One stable radix sort of (key, id) pairs by the keys' low `bits` bits, ascending: the size query,
+// `temp` grown to it (kept by its owner between calls), the sort.
+int sortPairs(DevBuf& temp, const uint32_t* keys, uint32_t* keys2, const uint32_t* ids, uint32_t* ids2, size_t n, int bits,
+              hipStream_t st) {
+    size_t bytes = 0;
+    HIP_TRY(pt::radixSortPairs(nullptr, &bytes, keys, keys2, ids, ids2, n, bits, st));
+    if (int rc = devReserve(temp, bytes)) return rc;
+    HIP_TRY(pt::radixSortPairs(temp.p, &bytes, keys, keys2, ids, ids2, n, bits, st));
+    return PT_OK;
 }
 
 // Events of a synchronous device step; on an early return (ok still false) the stream's queued
@@ -3921,13 +3901,7 @@ struct StreamWait {
     }
 };
 
-int stackFor(int depth) {
-    const int need = depth + 1;
-    for (int s : {16, 24, 32, 48, 64, 80})
-        if (need <= s) return s;
-    return -1;
-}
-
+// (stackFor: host/pt_render_plan.hpp)
 // The instanced scene's host tree build, mixLimit and wideStackFor: host/pt_instancing.cpp
 using pt::InstEntry;
 using pt::instanceInverse;
@@ -4384,7 +4358,8 @@ int setDevice(int dev) {
 // bytes of LDS leave five waves per SIMD (the 24-entry stack's 20 waves would need 165 KB of 160).
 template <int S, bool TRI>
 constexpr bool kAheadFor = TRI && S <= 16;
-inline bool aheadStack(int stack) { return stack == 8 || stack == 16; }
+static_assert(kAheadFor<8, true> && kAheadFor<16, true> && !kAheadFor<24, true> && pt::aheadStack(8) && pt::aheadStack(16) &&
+                  !pt::aheadStack(24), "the launch plan's aheadStack (host/pt_render_plan.hpp) names the AHEAD instantiations");
 // Sample mode on a flat scene.  TRI = P.tri: the triangle-only instantiations.
 template <int S, bool LIT, bool TRI>
 void launchSampleWideFlat(const RenderParams& P, hipStream_t st) {
@@ -4498,6 +4473,23 @@ int persistentWavesPerCU(int stack, int kernel, int& n, bool inst, bool sample, 
     });
     if (!ok) return fail(PT_ERR_STATE, !wide ? "unsupported BVH depth" : inst ? "unsupported instanced BVH depth" : "unsupported wide BVH depth");
     return rc;
+}
+// persistentWavesPerCU, asked once per (device, kernel instantiation) and process: its own argument
+// list after the device, so the cache's key and the query cannot drift apart.  Stacks of 8, 16 and 24
+// on devices 0..15 have a slot; the binary tree's deeper stacks (32 .. 80) have none and ask on every call.
+int cachedWavesPerCU(int device, int stack, int kernel, int& n, bool inst, bool sample, bool nee, bool mis, bool tri, bool ahead) {
+    static std::atomic<int> cached[16][2][2][2][3][3][2][2];   // [device][sample][instanced][wide][stack 8, 16, 24][blind, nee, mis][tri][ahead]
+    const bool small = stack <= 24 && stack % 8 == 0 && device >= 0 && device < 16;
+    std::atomic<int>* c = small ? &cached[device][sample ? 1 : 0][inst ? 1 : 0][kernel == PT_KERNEL_WIDE ? 1 : 0][stack / 8 - 1]
+                                         [mis ? 2 : nee ? 1 : 0][tri ? 1 : 0][ahead ? 1 : 0] : nullptr;
+    const int known = c ? c->load(std::memory_order_relaxed) : 0;
+    if (known > 0) {
+        n = known;
+        return PT_OK;
+    }
+    if (int r = persistentWavesPerCU(stack, kernel, n, inst, sample, nee, mis, tri, ahead)) return r;
+    if (c) c->store(n, std::memory_order_relaxed);
+    return PT_OK;
 }
 int dispatchRender(int stack, const RenderParams& P, hipStream_t st) {
     const bool wide = P.kernel == PT_KERNEL_WIDE;
@@ -4659,6 +4651,308 @@ int filmStats(pt_film* f, pt_stats* stats) {
     fillStats(stats, c, ms, f->lastWide);
     if (std::getenv("PT_ITER_STATS")) printIterStats(c, f->lastWide);
     if (c[7]) return fail(PT_ERR_STATE, "traversal guard tripped (corrupt BVH), flags " + std::to_string(c[7]));
+    return PT_OK;
+}
+
+// ------------------------------------------------------------------ pt_render_ex's stages
+// What the launch plan (host/pt_render_plan.hpp) reads of the scene, the film and the call.
+pt::RenderFacts renderFacts(const pt_scene* s, const pt_film* f, const pt_camera* cam, int spp, int max_depth,
+                            const pt_render_opts* opts) {
+    pt::RenderFacts F;
+    F.instanced = s->instanced;
+    F.instLights = s->instLights;
+    F.hasSpheres = s->hasSpheres;
+    F.hasEmissive = s->hasEmissive;
+    F.lambertOnly = s->lambertOnly;
+    F.wideReady = s->wideReady;
+    F.haveWtris = s->haveWtris;
+    F.nobj = s->nobj;
+    F.nLights = s->nLights;
+    F.depth = s->depth;
+    F.wideDepth = s->wideDepth;
+    std::memcpy(F.sceneCE, s->sceneCE, sizeof(F.sceneCE));
+    std::memcpy(F.skyH, s->skyH, sizeof(F.skyH));
+    std::memcpy(F.skyZ, s->skyZ, sizeof(F.skyZ));
+    F.width = f->width;
+    F.height = f->height;
+    F.nrows = f->nrows;
+    F.stripe_h = f->stripe_h;
+    F.npix = f->npix;
+    F.haveOrder = f->haveOrder;
+    F.framesSinceCost = f->framesSinceCost;
+    F.critK = f->critK;
+    F.accumSamples = f->accumSamples;
+    F.cam = cam;
+    F.spp = spp;
+    F.max_depth = max_depth;
+    F.opts = opts;
+    return F;
+}
+
+// What one call's stages hand on beside the plan.
+struct RenderCall {
+    hipStream_t st = 0;
+    void* dst = nullptr;          // the frame on the device: the caller's `out`, or the film's staging copy
+    size_t outBpp = 12;
+    int nwaves = 0;               // sample mode: persistent waves
+    bool newAccum = false;        // this call allocated the running sums: they are cleared with the frame
+    const char* timesPath = nullptr;   // PT_WAVE_TIMES (diagnostic): per-wave timestamps
+    size_t timeSlots = 0;         // = grid size
+    DevBuf dtimes;
+};
+
+// Film resources, allocated once and reused by every later render (no hipMalloc / hipFree,
+// which synchronise the device, in the per-frame path).  Enqueues nothing.
+int reserveFilm(const pt_scene* s, pt_film* f, const pt::RenderOptions& o, const pt::RenderPlan& plan, bool on_dev, RenderCall& c) {
+    int rc = PT_OK;
+    const int64_t np = f->npix;
+    if (!f->ev0) {
+        HIP_TRY(hipEventCreate(&f->ev0));
+        HIP_TRY(hipEventCreate(&f->ev1));
+        HIP_TRY(hipEventCreateWithFlags(&f->ev2, hipEventDisableTiming));
+    }
+    if (!f->counters.p && (rc = devAlloc(f->counters, kNumCounters * sizeof(unsigned long long)))) return rc;
+    if (!f->hostCounters) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&f->hostCounters),
+                                                kNumCounters * sizeof(unsigned long long), hipHostMallocDefault));
+    if (!on_dev) {
+        if ((rc = devReserve(f->staging, (size_t)std::max<int64_t>(1, np) * c.outBpp))) return rc;
+        c.dst = f->staging.p;
+    }
+    const size_t ntl = (size_t)std::max(1, plan.ntiles);
+    if (!f->tileCost.p) {
+        if ((rc = devAlloc(f->tileCost, ntl * 4)) || (rc = devAlloc(f->tileOrder, ntl * 4)) ||
+            (rc = devAlloc(f->tileXY, ntl * 4)) || (rc = devAlloc(f->tileXYId, ntl * 4)))
+            return rc;
+        f->haveOrder = false;
+    }
+    if (!f->cus) {
+        if (hipDeviceGetAttribute(&f->cus, hipDeviceAttributeMultiprocessorCount, f->device) != hipSuccess)
+            f->cus = 256;
+        f->cus = std::max(f->cus, 1);
+    }
+    if (plan.critOn && (rc = devReserve(f->pixRays, (size_t)np * 4))) return rc;
+    if (plan.sample) {
+        if ((rc = devReserve(f->pixAcc, (size_t)np * 32))) return rc;   // {x, y, z, rays} per pixel
+        if (!f->taskCounter.p && (rc = devAlloc(f->taskCounter, 64))) return rc;
+        int perCU = 0;
+        if ((rc = cachedWavesPerCU(f->device, plan.stack, o.kernel, perCU, s->instanced, plan.sample, o.nee, o.mis, plan.tri != 0,
+                                   plan.ahead != 0)))
+            return rc;
+        if ((rc = pt::persistentWaves(f->cus, perCU, plan.ntasks, c.nwaves))) return rc;
+        if (std::getenv("PT_ITER_STATS"))
+            std::fprintf(stderr, "[pt] persistent waves %d (%d per CU, stack %d)\n", c.nwaves, perCU, plan.stack);
+    }
+    if (plan.spillEntries > 0 &&
+        (rc = devReserve(f->stackSpill, plan.stackSpillBytes(plan.sample ? (size_t)c.nwaves : (size_t)plan.compatGrid))))
+        return rc;
+    if (plan.rawOut && !f->sums.p && (rc = devAlloc(f->sums, (size_t)np * 12))) return rc;
+    if (o.accumulate && !f->accum.p) {
+        if ((rc = devAlloc(f->accum, (size_t)std::max<int64_t>(1, np) * 12))) return rc;
+        f->accumSamples = 0;
+        c.newAccum = true;
+    }
+    c.timesPath = std::getenv("PT_WAVE_TIMES");
+    c.timeSlots = plan.sample ? (size_t)c.nwaves : (o.kernel != PT_KERNEL_SIMPLE ? (size_t)std::max(1, plan.compatGrid) : ntl);
+    if (c.timesPath && *c.timesPath && o.kernel != PT_KERNEL_SIMPLE && (rc = devAlloc(c.dtimes, c.timeSlots * 24))) return rc;
+    return PT_OK;
+}
+
+// The kernels' argument: every field, in the struct's order.
+void fillRenderParams(RenderParams& P, const pt_scene* s, const pt_film* f, const pt_camera* cam, int spp, int max_depth,
+                      const pt::RenderOptions& o, const pt::RenderPlan& plan, const RenderCall& c) {
+    const int64_t np = f->npix;
+    const bool tileOrder = o.lpt && f->haveOrder;
+    P.S = devScene(s);
+    P.S.err = reinterpret_cast<unsigned int*>(f->counters.as<unsigned long long>() + 7);
+    if (plan.triRecords) P.S.wprims = s->wtris.as<float4>();
+    P.cam.pos = make_float3(cam->origin[0], cam->origin[1], cam->origin[2]);
+    P.cam.ll = make_float3(cam->lower_left[0], cam->lower_left[1], cam->lower_left[2]);
+    P.cam.hor = make_float3(cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]);
+    P.cam.ver = make_float3(cam->vertical[0], cam->vertical[1], cam->vertical[2]);
+    P.cam.right = make_float3(cam->right[0], cam->right[1], cam->right[2]);
+    P.cam.up = make_float3(cam->up[0], cam->up[1], cam->up[2]);
+    P.cam.lens = cam->lens_radius;
+    uint32_t* b = f->state.as<uint32_t>();
+    P.sd = b; P.s0 = b + np; P.s1 = b + 2 * np; P.s2 = b + 3 * np; P.s3 = b + 4 * np; P.s4 = b + 5 * np;
+    P.out = plan.rawOut ? f->sums.as<float>() : static_cast<float*>(c.dst);
+    P.counters = f->counters.as<unsigned long long>();
+    P.width = f->width;
+    P.nrows = f->nrows;
+    P.stripe_h = f->stripe_h;
+    P.nparts = f->nparts;
+    P.part = f->part;
+    P.tiles_x = plan.tiles_x;
+    P.ntiles = plan.ntiles;
+    P.spp = spp;
+    P.max_depth = max_depth;
+    P.invW = 1.0f / (float)f->width;    // main.cu:281
+    P.invH = 1.0f / (float)f->height;
+    P.invSpp = 1.0f / (float)spp;
+    P.leafBatch = plan.leafBatch;
+    P.shadeBatch = plan.shadeBatch;
+    P.nodeMin = plan.nodeMin;
+    P.kernel = o.kernel;
+    P.waveTimes = c.dtimes.as<unsigned long long>();
+    P.tileOrder = tileOrder ? f->tileOrder.as<int>() : nullptr;
+    // sample mode: the launch order decoded per slot (tileXYKernel; the ordered table follows each sort)
+    P.tileXY = !plan.sample ? nullptr : tileOrder ? f->tileXY.as<uint32_t>() : f->tileXYId.as<uint32_t>();
+    P.nblocksShift = plan.nblocksShift;
+    P.tileCost = f->tileCost.as<unsigned>();
+    P.prioTiles = plan.prioTiles;
+    P.prioLevel = plan.prioLevel;
+    P.nblocks = plan.nblocks;
+    P.block = plan.block;
+    P.group = 1;
+    P.span = plan.span;
+    P.ngroups = plan.ngroups;
+    P.pixAcc = plan.sample ? f->pixAcc.as<unsigned long long>() : nullptr;
+    P.taskCounter = plan.sample ? f->taskCounter.as<unsigned>() : nullptr;
+    P.stackSpill = plan.spillEntries > 0 ? f->stackSpill.as<uint32_t>() : nullptr;
+    P.ntasks = plan.ntasks;
+    P.nwaves = c.nwaves;
+    P.seed0 = (uint32_t)f->seed;
+    P.seed1 = (uint32_t)(f->seed >> 32);
+    P.sampleBase = plan.sampleBase;
+    P.measureCost = plan.measureCost;
+    P.camFar = plan.camFar;
+    P.rawOut = plan.rawOut;
+    P.stripeShift = plan.stripeShift;
+    P.blockShift = plan.blockShift;
+    P.splitTiles = plan.splitTiles;
+    P.splitWays = plan.splitWays;
+    P.compatGrid = plan.compatGrid;
+    P.nCrit = plan.nCrit;
+    P.critLanes = plan.critLanes;
+    P.critWaves = plan.critWaves;
+    P.critList = plan.nCrit > 0 ? f->pixSorted.as<uint32_t>() : nullptr;
+    P.critFlag = plan.nCrit > 0 ? f->critFlag.as<uint8_t>() : nullptr;
+    P.pixRays = plan.critOn ? f->pixRays.as<uint32_t>() : nullptr;
+    P.skyH = make_float3(s->skyH[0], s->skyH[1], s->skyH[2]);
+    P.skyZ = make_float3(s->skyZ[0], s->skyZ[1], s->skyZ[2]);
+    P.lit = plan.lit;
+    P.lights = o.nee ? s->lights.as<float4>() : nullptr;
+    P.nLights = o.nee ? (int)s->nLights : 0;
+    P.mis = o.mis ? 1 : 0;
+    P.lightSlot = o.mis ? s->lightSlot.as<uint32_t>() : nullptr;   // (instanced: the ranks by shading index)
+    P.instLightFirst = o.mis && s->instanced ? s->instLightFirst.as<uint32_t>() : nullptr;
+    P.tri = plan.tri;
+    P.ahead = plan.ahead;
+}
+
+// The frame on the stream: the buffers' clears, the render kernel between the film's events, the
+// resolve pass, the counters' copy.  From its first event on the film describes this render.
+int enqueueFrame(pt_film* f, const RenderParams& P, int spp, const pt::RenderOptions& o, const pt::RenderPlan& plan,
+                 const RenderCall& c) {
+    int rc = PT_OK;
+    hipStream_t st = c.st;
+    const int64_t np = f->npix;
+    const size_t ntl = (size_t)std::max(1, plan.ntiles);
+    HIP_TRY(hipMemsetAsync(f->counters.p, 0, kNumCounters * sizeof(unsigned long long), st));
+    if (plan.sample) {
+        HIP_TRY(hipMemsetAsync(f->pixAcc.p, 0, (size_t)np * 32, st));
+        HIP_TRY(hipMemsetAsync(f->taskCounter.p, 0, 4, st));
+        f->framesSinceCost = plan.measureCost ? 0 : f->framesSinceCost + 1;
+        if (plan.measureCost) HIP_TRY(hipMemsetAsync(f->tileCost.p, 0, ntl * 4, st));
+    }
+    if (c.newAccum) HIP_TRY(hipMemsetAsync(f->accum.p, 0, (size_t)std::max<int64_t>(1, np) * 12, st));
+    if (plan.sample && !P.tileOrder && !f->haveXYId) {   // the identity order decoded, once
+        tileXYKernel<<<(unsigned)((ntl + 255) / 256), 256, 0, st>>>(nullptr, (int)ntl, P.tiles_x, f->tileXYId.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        f->haveXYId = true;
+    }
+    if (!plan.sample && o.kernel != PT_KERNEL_SIMPLE && P.ntiles > 0)   // (tile costs: atomicMax of the tile's waves)
+        HIP_TRY(hipMemsetAsync(f->tileCost.p, 0, ntl * 4, st));
+    if (P.waveTimes) HIP_TRY(hipMemsetAsync(c.dtimes.p, 0, c.timeSlots * 24, st));
+    // From here on the film describes this render (pt_film_stats reads it).
+    f->rendered = false;
+    f->lastWide = o.kernel == PT_KERNEL_WIDE;
+    HIP_TRY(hipEventRecord(f->ev0, st));
+    if (P.ntiles > 0 && (rc = dispatchRender(plan.stack, P, st))) return rc;
+    if (plan.resolve) {
+        const float inv = o.accumulate ? 1.0f / (float)(f->accumSamples + spp) : P.invSpp;
+        resolveKernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(f->sums.as<float>(), plan.sample ? P.pixAcc : nullptr,
+                                                                     o.accumulate ? f->accum.as<float>() : nullptr,
+                                                                     inv, o.fmt, c.dst, np,
+                                                                     P.measureCost ? f->tileCost.as<unsigned>() : nullptr,
+                                                                     f->width, P.tiles_x, envInt("PT_TILE_KEY_MAX", 1));
+        HIP_TRY(hipGetLastError());
+    }
+    if (o.accumulate) f->accumSamples += spp;
+    HIP_TRY(hipEventRecord(f->ev1, st));
+    // the counters to pinned host memory, in stream order (pt_film_stats waits for ev2 only)
+    HIP_TRY(hipMemcpyAsync(f->hostCounters, f->counters.p, kNumCounters * sizeof(unsigned long long),
+                           hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(f->ev2, st));
+    f->rendered = true;
+    return PT_OK;
+}
+
+// Ids 0 .. n-1 by descending cost (keys ~cost, ascending: tileKeyKernel), equal costs by ascending
+// id: a stable radix sort on the device.
+int sortByCostDescending(const DevBuf& cost, DevBuf& keys, DevBuf& keys2, DevBuf& ids, DevBuf& sorted, DevBuf& temp, size_t n,
+                         hipStream_t st) {
+    int rc = PT_OK;
+    if ((rc = devReserve(keys, n * 4)) || (rc = devReserve(keys2, n * 4)) || (rc = devReserve(ids, n * 4))) return rc;
+    tileKeyKernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(cost.as<unsigned>(), keys.as<uint32_t>(), ids.as<uint32_t>(), (int)n);
+    HIP_TRY(hipGetLastError());
+    return sortPairs(temp, keys.as<uint32_t>(), keys2.as<uint32_t>(), ids.as<uint32_t>(), sorted.as<uint32_t>(), n, 32, st);
+}
+
+// What the next launches start with: the longest tiles first, and (compat, wide kernel) the critical
+// pixels -- the K longest chains of this launch.
+int sortNextLaunch(pt_film* f, const pt::RenderOptions& o, const pt::RenderPlan& plan, hipStream_t st) {
+    int rc = PT_OK;
+    if (plan.sortTiles) {
+        const size_t ntl = (size_t)plan.ntiles;
+        if ((rc = sortByCostDescending(f->tileCost, f->tileKeys, f->tileKeys2, f->tileIds, f->tileOrder, f->sortTemp, ntl, st)))
+            return rc;
+        tileXYKernel<<<(unsigned)((ntl + 255) / 256), 256, 0, st>>>(f->tileOrder.as<uint32_t>(), (int)ntl, plan.tiles_x,
+                                                                    f->tileXY.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        f->haveOrder = true;
+    }
+    if (plan.critOn) {
+        const size_t n = (size_t)f->npix;
+        const int64_t K = std::min<int64_t>(envCount("PT_CRIT_PIXELS", pt::kCritPixels), f->npix);
+        if ((rc = devReserve(f->pixSorted, n * 4)) || (rc = devReserve(f->critFlag, n))) return rc;
+        if ((rc = sortByCostDescending(f->pixRays, f->pixKeys, f->pixKeys2, f->pixIds, f->pixSorted, f->critTemp, n, st))) return rc;
+        HIP_TRY(hipMemsetAsync(f->critFlag.p, 0, n, st));
+        critFlagKernel<<<(unsigned)((K + 255) / 256), 256, 0, st>>>(f->pixSorted.as<uint32_t>(), (int)K,
+                                                                   f->critFlag.as<uint8_t>());
+        HIP_TRY(hipGetLastError());
+        f->critK = (int)K;
+    }
+    return PT_OK;
+}
+
+// Diagnostics, each with a wait for the stream: PT_CHECK_ORDER (the launch order just sorted must be a
+// permutation of the tiles, by descending cost) and PT_WAVE_TIMES (the frame's per-wave timestamps to a file).
+int dumpDiagnostics(pt_film* f, const pt::RenderPlan& plan, const RenderCall& c) {
+    if (plan.sortTiles && std::getenv("PT_CHECK_ORDER")) {
+        const size_t ntl = (size_t)plan.ntiles;
+        std::vector<uint32_t> ord(ntl), cst(ntl);
+        HIP_TRY(hipStreamSynchronize(c.st));
+        HIP_TRY(hipMemcpy(ord.data(), f->tileOrder.p, ntl * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cst.data(), f->tileCost.p, ntl * 4, hipMemcpyDeviceToHost));
+        std::vector<uint8_t> seen(ntl, 0);
+        size_t dup = 0, bad = 0, unsorted = 0;
+        for (size_t k = 0; k < ntl; k++) {
+            if (ord[k] >= ntl) { bad++; continue; }
+            if (seen[ord[k]]++) dup++;
+            if (k && ord[k - 1] < ntl && cst[ord[k - 1]] < cst[ord[k]]) unsorted++;
+        }
+        std::fprintf(stderr, "[pt] tile order check: %zu tiles, %zu out of range, %zu duplicates, %zu unsorted pairs\n",
+                     ntl, bad, dup, unsorted);
+    }
+    if (c.dtimes.p) {
+        HIP_TRY(hipStreamSynchronize(c.st));
+        std::vector<unsigned long long> t(c.timeSlots * 3);
+        HIP_TRY(hipMemcpy(t.data(), c.dtimes.p, t.size() * 8, hipMemcpyDeviceToHost));
+        if (FILE* fp = std::fopen(c.timesPath, "wb")) {
+            std::fwrite(t.data(), 8, t.size(), fp);
+            std::fclose(fp);
+        }
+    }
     return PT_OK;
 }
 }  // namespace
@@ -4891,12 +5185,9 @@ int pt_scene_build_bvh_ex(pt_scene* s, int flags, void* stream) {
             mortonKernel<<<nb, tb, 0, st>>>(s->dobjs.as<pt_object>(), n, box6.as<float>(), codes.as<uint32_t>(),
                                             ids.as<uint32_t>());
             HIP_TRY(hipGetLastError());
-            size_t tbytes = 0;
-            HIP_TRY(pt::radixSortPairs(nullptr, &tbytes, codes.as<uint32_t>(), codes2.as<uint32_t>(),
-                                       ids.as<uint32_t>(), ids2.as<uint32_t>(), (size_t)n, 30, st));
-            if ((rc = devReserve(temp, tbytes))) return rc;
-            HIP_TRY(pt::radixSortPairs(temp.p, &tbytes, codes.as<uint32_t>(), codes2.as<uint32_t>(),
-                                       ids.as<uint32_t>(), ids2.as<uint32_t>(), (size_t)n, 30, st));
+            if ((rc = sortPairs(temp, codes.as<uint32_t>(), codes2.as<uint32_t>(), ids.as<uint32_t>(), ids2.as<uint32_t>(),
+                                (size_t)n, 30, st)))
+                return rc;
         }
         leafGatherKernel<<<nb, tb, 0, st>>>(s->dobjs.as<pt_object>(), codes2.as<uint32_t>(), ids2.as<uint32_t>(), n,
                                             s->keys.as<unsigned long long>(), s->prims.as<float4>(),
@@ -5530,418 +5821,27 @@ int pt_render_ex(pt_scene* s, pt_film* f, const pt_camera* cam, int spp, int max
         return fail(PT_ERR_INVALID, "pt_render: lens radius must be finite and >= 0");
     int rc = setDevice(s->device);
     if (rc) return rc;
-    hipStream_t st = on_dev ? (hipStream_t)stream : 0;
-    const int64_t np = f->npix;
-    const int fmt = opts ? opts->out_format : PT_OUT_RGB32F;
-    if (fmt != PT_OUT_RGB32F && fmt != PT_OUT_RGBA8 && fmt != PT_OUT_RGBA8_SURFACE)
-        return fail(PT_ERR_INVALID, "pt_render_ex: unknown output format");
-    const bool accumulate = opts && (opts->flags & PT_RENDER_ACCUMULATE);
-    const bool misFlag = opts && (opts->flags & PT_RENDER_MIS);   // (implies PT_RENDER_NEE)
-    const bool neeFlag = misFlag || (opts && (opts->flags & PT_RENDER_NEE));
-    const size_t outBpp = fmt == PT_OUT_RGB32F ? 12 : 4;
-    if (accumulate && f->accumSamples + spp >= (1ll << 24))
-        return fail(PT_ERR_INVALID, "pt_render_ex: accumulated samples must stay below 2^24");
-    // Kernel choice and wavefront-scheduler thresholds (lanes of 64): explicit options win, then
-    // the PT_RENDER_KERNEL / PT_LEAF_BATCH / PT_SHADE_BATCH environment (tuning), then defaults.
-    int kernel = opts ? opts->kernel : PT_KERNEL_DEFAULT;
-    if (kernel == PT_KERNEL_DEFAULT) {
-        const char* k = std::getenv("PT_RENDER_KERNEL");
-        const std::string ks = k ? k : "";
-        kernel = ks == "simple" ? PT_KERNEL_SIMPLE : (ks == "wavefront" ? PT_KERNEL_WAVEFRONT : PT_KERNEL_WIDE);
-    }
-    if (kernel != PT_KERNEL_SIMPLE && kernel != PT_KERNEL_WAVEFRONT && kernel != PT_KERNEL_WIDE)
-        return fail(PT_ERR_INVALID, "pt_render_ex: unknown kernel");
-    if (s->instanced && kernel != PT_KERNEL_WIDE)
-        return fail(PT_ERR_INVALID, "pt_render_ex: instanced scenes render with the wide kernel (PT_KERNEL_WIDE)");
-    if (misFlag && s->instanced && !s->instLights)   // (an instanced scene lists its lights on request: PT_BVH_LIGHTS)
-        return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_MIS is not available on instanced scenes (flat scenes only)");
-    if (misFlag && kernel == PT_KERNEL_WAVEFRONT)
-        return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_MIS is not available with PT_KERNEL_WAVEFRONT "
-                                    "(PT_KERNEL_WIDE, PT_KERNEL_DEFAULT or PT_KERNEL_SIMPLE)");
-    if (neeFlag && s->instanced && !s->instLights)
-        return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_NEE is not available on instanced scenes (flat scenes only)");
-    if (neeFlag && kernel == PT_KERNEL_WAVEFRONT)
-        return fail(PT_ERR_INVALID, "pt_render_ex: PT_RENDER_NEE is not available with PT_KERNEL_WAVEFRONT "
-                                    "(PT_KERNEL_WIDE, PT_KERNEL_DEFAULT or PT_KERNEL_SIMPLE)");
-    const bool nee = neeFlag && s->nLights > 0;   // (no sampled light: the flag changes nothing)
-    const bool mis = misFlag && nee;
-    const int rng = opts ? opts->rng : PT_RNG_COMPAT;
-    if (rng != PT_RNG_COMPAT && rng != PT_RNG_SAMPLE) return fail(PT_ERR_INVALID, "pt_render_ex: unknown rng mode");
-    if (kernel == PT_KERNEL_WIDE && (rc = ensureWide(s))) return rc;   // (first use: builds the tree)
-
-    // Film resources, allocated once and reused by every later render (no hipMalloc / hipFree,
-    // which synchronise the device, in the per-frame path).
-    if (!f->ev0) {
-        HIP_TRY(hipEventCreate(&f->ev0));
-        HIP_TRY(hipEventCreate(&f->ev1));
-        HIP_TRY(hipEventCreateWithFlags(&f->ev2, hipEventDisableTiming));
-    }
-    if (!f->counters.p && (rc = devAlloc(f->counters, kNumCounters * sizeof(unsigned long long)))) return rc;
-    if (!f->hostCounters) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&f->hostCounters),
-                                                kNumCounters * sizeof(unsigned long long), hipHostMallocDefault));
-    void* dst = out;
-    if (!on_dev) {
-        if ((rc = devReserve(f->staging, (size_t)std::max<int64_t>(1, np) * outBpp))) return rc;
-        dst = f->staging.p;
-    }
-    HIP_TRY(hipMemsetAsync(f->counters.p, 0, kNumCounters * sizeof(unsigned long long), st));
+    pt::RenderFacts facts = renderFacts(s, f, cam, spp, max_depth, opts);
+    pt::RenderOptions o;
+    if ((rc = pt::resolveRenderOptions(facts, o))) return rc;
+    if (o.kernel == PT_KERNEL_WIDE && (rc = ensureWide(s))) return rc;   // (first use: builds the tree)
+    facts = renderFacts(s, f, cam, spp, max_depth, opts);                // (the wide tree's depth and records)
+    pt::RenderPlan plan;
+    if ((rc = pt::planRender(facts, o, plan))) return rc;
+    if (o.kernel == PT_KERNEL_WIDE && s->nobj > 0 && (!s->wide.p || !(plan.triRecords ? s->wtris.p : s->wprims.p)))
+        return fail(PT_ERR_STATE, "wide BVH missing");
+    RenderCall c;
+    c.st = on_dev ? (hipStream_t)stream : 0;
+    c.outBpp = o.fmt == PT_OUT_RGB32F ? 12 : 4;
+    c.dst = out;
+    if ((rc = reserveFilm(s, f, o, plan, on_dev != 0, c))) return rc;
     RenderParams P;
-    P.S = devScene(s);
-    P.S.err = reinterpret_cast<unsigned int*>(f->counters.as<unsigned long long>() + 7);
-    // (the render kernels' triangle-only LEAF path reads edge-form records: DevScene::wprims)
-    // The kernels' TRI instantiations read nothing else, so they launch under this one condition
-    // (PT_WIDE_TRI=0: the generic kernels on the same records, for tests and same-library A/B runs).
-    const bool triRecords = s->wideReady && s->haveWtris && !s->hasSpheres && !s->instanced;
-    if (triRecords) P.S.wprims = s->wtris.as<float4>();
-    P.tri = triRecords && kernel == PT_KERNEL_WIDE && envCount("PT_WIDE_TRI", 1) != 0 ? 1 : 0;
-    P.cam.pos = make_float3(cam->origin[0], cam->origin[1], cam->origin[2]);
-    P.cam.ll = make_float3(cam->lower_left[0], cam->lower_left[1], cam->lower_left[2]);
-    P.cam.hor = make_float3(cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]);
-    P.cam.ver = make_float3(cam->vertical[0], cam->vertical[1], cam->vertical[2]);
-    P.cam.right = make_float3(cam->right[0], cam->right[1], cam->right[2]);
-    P.cam.up = make_float3(cam->up[0], cam->up[1], cam->up[2]);
-    P.cam.lens = cam->lens_radius;
-    P.skyH = make_float3(s->skyH[0], s->skyH[1], s->skyH[2]);
-    P.skyZ = make_float3(s->skyZ[0], s->skyZ[1], s->skyZ[2]);
-    {   // the LIT kernels only where they are needed: an emitter, or a sky that is not the reference's
-        static const float H0[3] = {1.0f, 1.0f, 1.0f}, Z0[3] = {0.5f, 0.7f, 1.0f};
-        P.lit = (s->hasEmissive || std::memcmp(s->skyH, H0, sizeof(H0)) != 0 || std::memcmp(s->skyZ, Z0, sizeof(Z0)) != 0) ? 1 : 0;
-    }
-    P.lights = nee ? s->lights.as<float4>() : nullptr;
-    P.nLights = nee ? (int)s->nLights : 0;
-    P.mis = mis ? 1 : 0;
-    P.lightSlot = mis ? s->lightSlot.as<uint32_t>() : nullptr;   // (instanced: the ranks by shading index)
-    P.instLightFirst = mis && s->instanced ? s->instLightFirst.as<uint32_t>() : nullptr;
-    uint32_t* b = f->state.as<uint32_t>();
-    P.sd = b; P.s0 = b + np; P.s1 = b + 2 * np; P.s2 = b + 3 * np; P.s3 = b + 4 * np; P.s4 = b + 5 * np;
-    P.out = static_cast<float*>(dst);
-    P.rawOut = 0;
-    P.sampleBase = 0;
-    P.counters = f->counters.as<unsigned long long>();
-    P.width = f->width;
-    P.nrows = f->nrows;
-    P.stripe_h = f->stripe_h;
-    P.stripeShift = (f->stripe_h & (f->stripe_h - 1)) == 0 ? __builtin_ctz((unsigned)f->stripe_h) : -1;
-    P.nparts = f->nparts;
-    P.part = f->part;
-    P.tiles_x = (f->width + 7) / 8;
-    P.ntiles = P.tiles_x * ((f->nrows + 7) / 8);
-    P.spp = spp;
-    P.max_depth = max_depth;
-    P.invW = 1.0f / (float)f->width;    // main.cu:281
-    P.invH = 1.0f / (float)f->height;
-    P.invSpp = 1.0f / (float)spp;
-    if (kernel == PT_KERNEL_WIDE && s->nobj > 0 && (!P.S.wnodes || !P.S.wprims)) return fail(PT_ERR_STATE, "wide BVH missing");
-    P.kernel = kernel;
-    P.nblocks = 0;
-    P.block = 0;
-    P.blockShift = -1;
-    P.group = 1;
-    P.span = 0;
-    P.ngroups = 0;
-    P.pixAcc = nullptr;
-    P.taskCounter = nullptr;
-    P.stackSpill = nullptr;
-    P.ntasks = 0;
-    P.nwaves = 0;
-    P.seed0 = (uint32_t)f->seed;
-    P.seed1 = (uint32_t)(f->seed >> 32);
-    P.measureCost = 0;
-    {   // wideFar (pt_device.hip) for the camera: its rays then take the reference-order path
-        // (instanced scenes: start at their entry into the world, instEntry).  A lens sample moves
-        // the origin by lens * (x right + y up) with x^2 + y^2 < 1, i.e. by at most
-        // lens * (|right_a| + |up_a|) on axis a, whatever right / up the caller filled in.
-        double m = 0.0;
-        for (int a = 0; a < 3; a++)
-            m = std::max(m, std::fabs((double)cam->origin[a] - (double)s->sceneCE[a]) +
-                                (double)cam->lens_radius * (std::fabs((double)cam->right[a]) + std::fabs((double)cam->up[a])));
-        P.camFar = !(m <= (s->instanced ? (double)kInstFarExt : (double)kWideFarExt) * (double)s->sceneCE[3]) ? 1 : 0;
-    }
-    // Defaults swept on C3 (tools/ab_env.py): sample mode is throughput-bound and prefers full
-    // LEAF / SHADE steps.  Compat mode on the binary tree is bound by its slowest pixels' sequential
-    // chains: 20 / 12 together with nodeMin 8 (C3 1,521 -> 1,442 ms, C2 90.7 -> 80.0, C5 1,311 ->
-    // 1,180 against 8 / 12).  Compat on the flattened wide tree, since round 6 (its critical chains
-    // in critical-pixel waves, or short paths): the sample mode's wide thresholds with nodeMin 8 --
-    // C3 @1024 (critical pixels on) 705 -> 649 ms (SHADE 28 alone 665, 20 674; LEAF 28 alone 695),
-    // C5 @512 558 -> 539 (24 / 24), C2 @256 37.7 -> 37.1; nodeMin 0 740 / 617 ms, 4: 656 on C3.
-    const bool sampleRng = rng == PT_RNG_SAMPLE;
-    // sample mode, wide kernel (speculative traversal): LEAF at 28 waiting lanes, SHADE at 28
-    // (C3 @256 spp 148.4 -> 145.0 ms vs 24 / 32; C5 @64 75.9 -> 74.5; C2 @1024 135.4 -> 134.5);
-    // deep wide trees (a 16+ entry stack: C5's 1.04 M triangles) at 24 / 24 (round 3 close: C5 @64
-    // 67.1 -> 65.1 ms, median of 5; C3 at 24 / 24 is 1 % slower, so shallow trees keep 28 / 28)
-    const bool wideSample = sampleRng && kernel == PT_KERNEL_WIDE;
-    const bool wideFlatCompat = !sampleRng && kernel == PT_KERNEL_WIDE && !s->instanced;
-    const int stack = kernel == PT_KERNEL_WIDE ? wideStackFor(s->wideDepth) : (s->nobj > 1 ? stackFor(s->depth) : 16);
-    const int wideBatch = stack >= 16 ? 24 : 28;
-    // instanced scenes (no speculative traversal: a lane with primitives waiting cannot visit nodes)
-    // take their LEAF steps earlier: LEAF 16 / SHADE 20 (round 5, C5 instanced @128 spp, interleaved
-    // median of 3: 131.8 -> 128.8 ms; LEAF 12: 131.8, 8: 135.9, 32: 140.7; SHADE 28 with LEAF 16: 131.4)
-    // (instanced compat takes them too: C5 instanced compat @512 618.6 -> 594.6 ms; 24 / 24: 609.8,
-    // 28 / 28: 646.5)
-    const bool instWide = kernel == PT_KERNEL_WIDE && s->instanced;
-    P.leafBatch = (opts && opts->leaf_batch > 0) ? std::min(opts->leaf_batch, 64)
-                                                 : envInt("PT_LEAF_BATCH", instWide ? 16 : (wideSample || wideFlatCompat) ? wideBatch
-                                                                                                       : (sampleRng ? 24 : 20));
-    // compat mode: a NODE step with fewer than nodeMin lanes yields to the larger of the waiting
-    // LEAF / SHADE groups (C3 compat 1,620 -> 1,517 ms at 8; 4: 1,548, 16: 1,671, 32: 1,989)
-    P.nodeMin = std::getenv("PT_NODE_MIN") ? std::atoi(std::getenv("PT_NODE_MIN")) : 8;
-    P.shadeBatch = (opts && opts->shade_batch > 0) ? std::min(opts->shade_batch, 64)
-                                                   : envInt("PT_SHADE_BATCH", instWide ? 20 : (wideSample || wideFlatCompat) ? wideBatch
-                                                                                                           : (sampleRng ? 32 : 12));
-    if (kernel == PT_KERNEL_SIMPLE) P.leafBatch = 0;
-    const size_t ntl = (size_t)std::max(1, P.ntiles);
-    if (!f->tileCost.p) {
-        if ((rc = devAlloc(f->tileCost, ntl * 4)) || (rc = devAlloc(f->tileOrder, ntl * 4)) ||
-            (rc = devAlloc(f->tileXY, ntl * 4)) || (rc = devAlloc(f->tileXYId, ntl * 4)))
-            return rc;
-        f->haveOrder = false;
-    }
-    const bool lpt = !(opts && (opts->flags & PT_RENDER_IDENTITY_ORDER));
-    const bool sample = rng == PT_RNG_SAMPLE && np > 0 && P.ntiles > 0;
-    // The AHEAD kernels: a triangle-only flat scene in sample mode on the wide kernel, no material that
-    // draws outside the unit-sphere loop, a pinhole camera, no light sampling, a stack they are built for
-    // (PT_SHADE_AHEAD=0: today's kernels in the same library, for tests and A/B runs).
-    P.ahead = sample && P.tri && s->lambertOnly && cam->lens_radius == 0.0f && !nee && aheadStack(stack) &&
-                      envCount("PT_SHADE_AHEAD", 1) != 0 ? 1 : 0;
-    if (!f->cus) {
-        if (hipDeviceGetAttribute(&f->cus, hipDeviceAttributeMultiprocessorCount, f->device) != hipSuccess)
-            f->cus = 256;
-        f->cus = std::max(f->cus, 1);
-    }
-    // persistent waves (sample mode): exactly the waves that fit at once -- the kernel's
-    // occupancy per CU, which the LDS stack caps on deep trees.  Queried once per (device, kernel
-    // instantiation) and process.
-    auto perCUFor = [&](int& perCU) -> int {
-        static std::atomic<int> cached[16][2][2][2][3][3][2][2];   // [device][sample][instanced][wide][stack 8, 16, 24][blind, nee, mis][tri][ahead]
-        const bool small = stack <= 24 && stack % 8 == 0 && f->device >= 0 && f->device < 16;
-        std::atomic<int>* c = small ? &cached[f->device][sample ? 1 : 0][s->instanced ? 1 : 0]
-                                             [kernel == PT_KERNEL_WIDE ? 1 : 0][stack / 8 - 1][mis ? 2 : nee ? 1 : 0][P.tri][P.ahead] : nullptr;
-        const int known = c ? c->load(std::memory_order_relaxed) : 0;
-        if (known > 0) {
-            perCU = known;
-            return PT_OK;
-        }
-        if (int r = persistentWavesPerCU(stack, kernel, perCU, s->instanced, sample, nee, mis, P.tri != 0, P.ahead != 0)) return r;
-        if (c) c->store(perCU, std::memory_order_relaxed);
-        return PT_OK;
-    };
-    // compat critical pixels (wide kernel, flattened scene, long paths): the previous launch's
-    // PT_CRIT_PIXELS longest per-pixel chains run first, PT_CRIT_LANES pixels per wave, each lane
-    // tracing its rays in one per-lane loop (a lane alone on its chain is not held back by the wave's
-    // step kinds).  C3 compat @1024 (interleaved, median of 2): 773 ms without; 256 x 4 699 ms;
-    // 64 x 1 710, 128 x 4 707, 512 x 4 712, 256 x 8 751 (with the split tiles as well).  The rays
-    // per pixel are measured on every launch.
-    P.nCrit = 0;
-    P.critLanes = std::max(1, std::min(64, envCount("PT_CRIT_LANES", kCritLanes)));
-    P.critWaves = 0;
-    P.critList = nullptr;
-    P.critFlag = nullptr;
-    P.pixRays = nullptr;
-    // (not in NEE launches: the per-lane loop knows no shadow query; the waves only schedule)
-    const bool critOn = lpt && !nee && critFor(sample, kernel == PT_KERNEL_WIDE, s->instanced, stack) && np > 0 &&
-                        max_depth > 16 && envCount("PT_CRIT_PIXELS", kCritPixels) > 0;
-    if (critOn) {
-        if ((rc = devReserve(f->pixRays, (size_t)np * 4))) return rc;
-        P.pixRays = f->pixRays.as<uint32_t>();
-        if (f->critK > 0) {
-            P.nCrit = f->critK;
-            P.critWaves = (P.nCrit + P.critLanes - 1) / P.critLanes;
-            P.critList = f->pixSorted.as<uint32_t>();
-            P.critFlag = f->critFlag.as<uint8_t>();
-        }
-    }
-    // compat tile waves: the longest tiles of the launch order split into splitWays waves (renderKernelWF).
-    // Only where a pixel's sequential chain can outlast the frame's throughput-bound part: long paths
-    // (max_depth > 16; C3, depth 50: 800 -> 766 ms) on kernels without critical-pixel waves, which
-    // take those chains out of the tile waves (C3 with both: 710 ms, critical pixels alone 699 ms).
-    // Short-path frames are throughput-bound and the split's idle lanes cost (C5, depth 16: 548 ->
-    // 553 ms; C2, depth 8: +0.9 %).
-    P.splitWays = std::max(1, std::min(8, envCount("PT_SPLIT_WAYS", 2)));
-    P.splitTiles = (lpt && f->haveOrder && !sample && kernel != PT_KERNEL_SIMPLE)
-                       ? std::max(0, std::min(P.ntiles, envCount("PT_SPLIT_TILES", max_depth > 16 && !critOn ? 128 : 0))) : 0;
-    if (P.splitWays == 1) P.splitTiles = 0;
-    P.compatGrid = P.critWaves + P.ntiles + P.splitTiles * (P.splitWays - 1);
-    // diagnostic: only the first k waves of the launch order (the longest tiles) -- their chains'
-    // latency with the machine otherwise idle; the other pixels are not rendered
-    if (const int lim = envCount("PT_COMPAT_GRID_LIMIT", 0)) P.compatGrid = std::min(P.compatGrid, lim);
-    if (sample) {
-        if (f->width >= 65536 || f->nrows >= 65536)
-            return fail(PT_ERR_INVALID, "sample mode: frame width and rows must be < 65536");
-        P.block = (opts && opts->chunk > 0) ? opts->chunk : std::max(16, (spp + 63) / 64);
-        P.nblocks = (spp + P.block - 1) / P.block;
-        P.blockShift = (P.block & (P.block - 1)) == 0 ? __builtin_ctz((unsigned)P.block) : -1;
-        P.span = P.block;   // one summation block per task
-        P.ngroups = P.nblocks;
-        const uint64_t ntasks = (uint64_t)P.ntiles * (uint64_t)P.ngroups * 64u;
-        // The 32-bit task counter (PT_TAKE_TASKS) runs past ntasks: every persistent wave takes
-        // exactly one pool of kTaskPool = 64 after the tasks are gone (its lanes each ask once more
-        // and share it), so the counter ends at ntasks + 64 * nwaves and must not wrap on the way --
-        // a wrapped grab would hand out task 0 again.  The limit leaves room for kMaxPersistentWaves
-        // such pools whatever the device (pt.h states it); the launch's nwaves is checked below.
-        constexpr uint64_t kMaxPersistentWaves = 1ull << 20;
-        constexpr uint64_t kTaskLimit = (1ull << 32) - (uint64_t)kTaskPool * kMaxPersistentWaves;   // 2^32 - 2^26
-        if (ntasks >= kTaskLimit)
-            return fail(PT_ERR_INVALID, "sample mode: too many (pixel, block) tasks (tiles x blocks x 64 must stay "
-                                        "below 2^32 - 2^26); raise the block size (chunk)");
-        P.ntasks = (uint32_t)ntasks;
-        if ((rc = devReserve(f->pixAcc, (size_t)np * 32))) return rc;   // {x, y, z, rays} per pixel
-        HIP_TRY(hipMemsetAsync(f->pixAcc.p, 0, (size_t)np * 32, st));
-        P.pixAcc = f->pixAcc.as<unsigned long long>();
-        if (!f->taskCounter.p && (rc = devAlloc(f->taskCounter, 64))) return rc;
-        HIP_TRY(hipMemsetAsync(f->taskCounter.p, 0, 4, st));
-        P.taskCounter = f->taskCounter.as<unsigned>();
-        int perCU = 0;
-        if ((rc = perCUFor(perCU))) return rc;
-        const uint64_t full = (uint64_t)f->cus * (uint64_t)std::max(1, perCU);
-        P.nwaves = (int)std::min<uint64_t>(full, (ntasks + 63) / 64);
-        if ((uint64_t)P.nwaves > kMaxPersistentWaves)
-            return fail(PT_ERR_STATE, "sample mode: more persistent waves than the task limit leaves room for");
-        if (std::getenv("PT_ITER_STATS"))
-            std::fprintf(stderr, "[pt] persistent waves %d (%d per CU, stack %d)\n", P.nwaves, perCU, stack);
-        // Tile costs (rays of the tile's most expensive pixel) are measured on the first frame and
-        // then on one frame in eight: the order only steers the launch's tail, and counting costs
-        // one more atomic per task.
-        P.measureCost = (lpt && (!f->haveOrder || f->framesSinceCost >= 7)) ? 1 : 0;
-        f->framesSinceCost = P.measureCost ? 0 : f->framesSinceCost + 1;
-        if (P.measureCost) HIP_TRY(hipMemsetAsync(f->tileCost.p, 0, ntl * 4, st));
-    }
-    // Deep trees: stack entries beyond kLdsStack live in memory, per wave slot (persistent wave or
-    // compat tile) and lane
-    if (kernel == PT_KERNEL_WAVEFRONT && stack > PT_LDS_STACK && P.ntiles > 0) {
-        const size_t slots = sample ? (size_t)P.nwaves : (size_t)P.compatGrid;
-        if ((rc = devReserve(f->stackSpill, slots * kWave * (size_t)(stack - PT_LDS_STACK) * 4))) return rc;
-        P.stackSpill = f->stackSpill.as<uint32_t>();
-    }
-    // A resolve pass follows the render kernel in sample mode (block sums) and whenever the film
-    // accumulates or the output is 8-bit; compat kernels then store raw sums into f->sums.
-    const bool resolve = np > 0 && (sample || accumulate || fmt != PT_OUT_RGB32F);
-    if (resolve && !sample) {
-        if (!f->sums.p && (rc = devAlloc(f->sums, (size_t)np * 12))) return rc;
-        P.out = f->sums.as<float>();
-        P.rawOut = 1;
-    }
-    if (accumulate) {
-        if (!f->accum.p) {
-            if ((rc = devAlloc(f->accum, (size_t)std::max<int64_t>(1, np) * 12))) return rc;
-            HIP_TRY(hipMemsetAsync(f->accum.p, 0, (size_t)std::max<int64_t>(1, np) * 12, st));
-            f->accumSamples = 0;
-        }
-        if (sample) P.sampleBase = (uint32_t)f->accumSamples;   // frames continue the sample sequence
-    }
-    P.tileCost = f->tileCost.as<unsigned>();
-    P.tileOrder = (lpt && f->haveOrder) ? f->tileOrder.as<int>() : nullptr;
-    P.tileXY = nullptr;
-    P.nblocksShift = -1;
-    if (sample) {   // the launch order decoded per slot (tileXYKernel; the ordered table follows each sort)
-        P.nblocksShift = (P.ngroups & (P.ngroups - 1)) == 0 ? __builtin_ctz((unsigned)P.ngroups) : -1;
-        if (!P.tileOrder && !f->haveXYId) {
-            tileXYKernel<<<(unsigned)((ntl + 255) / 256), 256, 0, st>>>(nullptr, (int)ntl, P.tiles_x, f->tileXYId.as<uint32_t>());
-            HIP_TRY(hipGetLastError());
-            f->haveXYId = true;
-        }
-        P.tileXY = P.tileOrder ? f->tileXY.as<uint32_t>() : f->tileXYId.as<uint32_t>();
-    }
-    P.prioTiles = (P.tileOrder && !sample) ? envCount("PT_PRIO_TILES", 1024) : 0;
-    P.prioLevel = std::max(1, std::min(3, envCount("PT_PRIO_LEVEL", 2)));
-    if (!sample && kernel != PT_KERNEL_SIMPLE && P.ntiles > 0)   // (tile costs: atomicMax of the tile's waves)
-        HIP_TRY(hipMemsetAsync(f->tileCost.p, 0, ntl * 4, st));
-    DevBuf dtimes;
-    const char* timesPath = std::getenv("PT_WAVE_TIMES");   // diagnostic: per-wave timestamps
-    P.waveTimes = nullptr;
-    const size_t nwaves = sample ? (size_t)P.nwaves
-                        : (kernel != PT_KERNEL_SIMPLE ? (size_t)std::max(1, P.compatGrid) : ntl);   // = grid size
-    if (timesPath && *timesPath && kernel != PT_KERNEL_SIMPLE) {
-        if ((rc = devAlloc(dtimes, nwaves * 24))) return rc;
-        HIP_TRY(hipMemsetAsync(dtimes.p, 0, nwaves * 24, st));
-        P.waveTimes = dtimes.as<unsigned long long>();
-    }
-    // From here on the film describes this render (pt_film_stats reads it).
-    f->rendered = false;
-    f->lastWide = kernel == PT_KERNEL_WIDE;
-    HIP_TRY(hipEventRecord(f->ev0, st));
-    if (P.ntiles > 0 && (rc = dispatchRender(stack, P, st))) return rc;
-    if (resolve) {
-        const float inv = accumulate ? 1.0f / (float)(f->accumSamples + spp) : P.invSpp;
-        resolveKernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(f->sums.as<float>(), sample ? P.pixAcc : nullptr,
-                                                                     accumulate ? f->accum.as<float>() : nullptr,
-                                                                     inv, fmt, dst, np,
-                                                                     P.measureCost ? f->tileCost.as<unsigned>() : nullptr,
-                                                                     f->width, P.tiles_x, envInt("PT_TILE_KEY_MAX", 1));
-        HIP_TRY(hipGetLastError());
-    }
-    if (accumulate) f->accumSamples += spp;
-    HIP_TRY(hipEventRecord(f->ev1, st));
-    // the counters to pinned host memory, in stream order (pt_film_stats waits for ev2 only)
-    HIP_TRY(hipMemcpyAsync(f->hostCounters, f->counters.p, kNumCounters * sizeof(unsigned long long),
-                           hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(f->ev2, st));
-    f->rendered = true;
-    if (lpt && P.ntiles > 0 && (!sample || P.measureCost)) {   // next launches: longest tiles first (a stable radix sort, on the device)
-        const int nt = (int)ntl;
-        if ((rc = devReserve(f->tileKeys, ntl * 4)) || (rc = devReserve(f->tileKeys2, ntl * 4)) ||
-            (rc = devReserve(f->tileIds, ntl * 4)))
-            return rc;
-        size_t tbytes = 0;
-        HIP_TRY(pt::radixSortPairs(nullptr, &tbytes, f->tileKeys.as<uint32_t>(), f->tileKeys2.as<uint32_t>(),
-                                   f->tileIds.as<uint32_t>(), f->tileOrder.as<uint32_t>(), ntl, 32, st));
-        if ((rc = devReserve(f->sortTemp, tbytes))) return rc;
-        tileKeyKernel<<<(unsigned)((nt + 255) / 256), 256, 0, st>>>(f->tileCost.as<unsigned>(), f->tileKeys.as<uint32_t>(),
-                                                                    f->tileIds.as<uint32_t>(), nt);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(pt::radixSortPairs(f->sortTemp.p, &tbytes, f->tileKeys.as<uint32_t>(), f->tileKeys2.as<uint32_t>(),
-                                   f->tileIds.as<uint32_t>(), f->tileOrder.as<uint32_t>(), ntl, 32, st));
-        tileXYKernel<<<(unsigned)((nt + 255) / 256), 256, 0, st>>>(f->tileOrder.as<uint32_t>(), nt, P.tiles_x,
-                                                                   f->tileXY.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        f->haveOrder = true;
-        if (std::getenv("PT_CHECK_ORDER")) {   // diagnostic: the launch order must be a permutation of the tiles
-            std::vector<uint32_t> ord(ntl), cst(ntl);
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipMemcpy(ord.data(), f->tileOrder.p, ntl * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(cst.data(), f->tileCost.p, ntl * 4, hipMemcpyDeviceToHost));
-            std::vector<uint8_t> seen(ntl, 0);
-            size_t dup = 0, bad = 0, unsorted = 0;
-            for (size_t k = 0; k < ntl; k++) {
-                if (ord[k] >= ntl) { bad++; continue; }
-                if (seen[ord[k]]++) dup++;
-                if (k && ord[k - 1] < ntl && cst[ord[k - 1]] < cst[ord[k]]) unsorted++;
-            }
-            std::fprintf(stderr, "[pt] tile order check: %zu tiles, %zu out of range, %zu duplicates, %zu unsorted pairs\n",
-                         ntl, bad, dup, unsorted);
-        }
-    }
-    if (critOn) {   // the next launch's critical pixels: the K longest chains of this one (a stable radix sort)
-        const int64_t K = std::min<int64_t>(envCount("PT_CRIT_PIXELS", kCritPixels), np);
-        const size_t n = (size_t)np;
-        if ((rc = devReserve(f->pixKeys, n * 4)) || (rc = devReserve(f->pixKeys2, n * 4)) ||
-            (rc = devReserve(f->pixIds, n * 4)) || (rc = devReserve(f->pixSorted, n * 4)) ||
-            (rc = devReserve(f->critFlag, n)))
-            return rc;
-        size_t cbytes = 0;
-        HIP_TRY(pt::radixSortPairs(nullptr, &cbytes, f->pixKeys.as<uint32_t>(), f->pixKeys2.as<uint32_t>(),
-                                   f->pixIds.as<uint32_t>(), f->pixSorted.as<uint32_t>(), n, 32, st));
-        if ((rc = devReserve(f->critTemp, cbytes))) return rc;
-        tileKeyKernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(f->pixRays.as<unsigned>(), f->pixKeys.as<uint32_t>(),
-                                                                  f->pixIds.as<uint32_t>(), (int)n);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(pt::radixSortPairs(f->critTemp.p, &cbytes, f->pixKeys.as<uint32_t>(), f->pixKeys2.as<uint32_t>(),
-                                   f->pixIds.as<uint32_t>(), f->pixSorted.as<uint32_t>(), n, 32, st));
-        HIP_TRY(hipMemsetAsync(f->critFlag.p, 0, n, st));
-        critFlagKernel<<<(unsigned)((K + 255) / 256), 256, 0, st>>>(f->pixSorted.as<uint32_t>(), (int)K,
-                                                                   f->critFlag.as<uint8_t>());
-        HIP_TRY(hipGetLastError());
-        f->critK = (int)K;
-    }
-    if (P.waveTimes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        std::vector<unsigned long long> t(nwaves * 3);
-        HIP_TRY(hipMemcpy(t.data(), dtimes.p, t.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE* fp = std::fopen(timesPath, "wb")) {
-            std::fwrite(t.data(), 8, t.size(), fp);
-            std::fclose(fp);
-        }
-    }
-    if (!on_dev && np > 0) HIP_TRY(hipMemcpy(out, dst, np * outBpp, hipMemcpyDeviceToHost));
+    fillRenderParams(P, s, f, cam, spp, max_depth, o, plan, c);
+    if ((rc = enqueueFrame(f, P, spp, o, plan, c))) return rc;
+    if ((rc = sortNextLaunch(f, o, plan, c.st))) return rc;
+    if ((rc = dumpDiagnostics(f, plan, c))) return rc;
+    const int64_t np = f->npix;
+    if (!on_dev && np > 0) HIP_TRY(hipMemcpy(out, c.dst, np * c.outBpp, hipMemcpyDeviceToHost));
     // With stats (or a host output) the call waits for the frame; without, it returns at once.
     if (stats || !on_dev) return filmStats(f, stats);
     return PT_OK;

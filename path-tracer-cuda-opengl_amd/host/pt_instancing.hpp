@@ -79,7 +79,7 @@ struct InstancedIn {
     bool dynamic;                // lay out for pt_scene_update_instances (reach x 2, top region at its cap)
     int rebraid;                 // PT_INST_REBRAID (0..3 levels) and PT_INST_ENTRIES (> 0: the entry
     int entryBudget;             // budget instead), read by the caller
-    float farExt;                // the kernels' instFar line in world extents (kInstFarExt, pt_device.hip)
+    float farExt;                // the kernels' instFar line in world extents (kInstFarExt, pt_render_plan.hpp)
 };
 
 // The world-to-object transform of one instance, in double and rounded to the fp32 rows the

@@ -95,8 +95,9 @@ def source_regions():
 
 def main() -> None:
     asm = sys.argv[1] if len(sys.argv) > 1 else "/tmp/isa/pt_device_g.s"
-    # (default: the flagship's triangle-only instantiation; ...ELb0ELb0ELb0ELb0ELb0EE is the generic one)
-    want = sys.argv[2] if len(sys.argv) > 2 else "renderKernelWFILi8ELb1ELb1ELb0ELb0ELb0ELb0ELb1EE"
+    # (default: the flagship's triangle-only AHEAD instantiation; ...ELb1ELb0EE is its twin without the slots,
+    # ...ELb0ELb0ELb0ELb0ELb0ELb0EE the generic one)
+    want = sys.argv[2] if len(sys.argv) > 2 else "renderKernelWFILi8ELb1ELb1ELb0ELb0ELb0ELb0ELb1ELb1EE"
     text = open(asm).read().split("\n")
     files = {}
     start = None
